@@ -12,6 +12,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
                 events on the launch stream, against the 8 TB/s HBM peak
   cpu_baseline  oracle/ (this repo's CPU restatement of the reference path, "port") timed on one host core
                 on a bounded sample of the same frames.
+
+A plain run sets up, warms up, times the steps and prints the line: parity against the oracle, cpu_baseline, the in-order
+kernel timing, the secondary figures and the other BASELINE configs come with --full only.  --dump-outputs DIR writes what
+the last timed step computed as .npy files (inputs are a function of the arguments, so two builds compare output for output).
 """
 import argparse
 import json
@@ -201,6 +205,31 @@ def _emit(full, args):
     s = json.dumps(line)
     assert len(s) <= LINE_LIMIT, len(s)
     print(s, flush=True)
+
+
+DUMP_LIMIT = 60 << 20      # bytes of .npy data --dump-outputs may write in all (a fixed sample of the rows beyond it)
+DUMP_SEED = 20251016
+
+
+def _dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: `arrays` = [(name, device tensor whose first axis is rows, numpy float dtype)] -- what the timed path handed
+    its caller in the last step -> `path`/<name>.npy.  Over DUMP_LIMIT (split evenly over the ranks), every array keeps the same fixed
+    fraction of its rows, drawn with a fixed seed (arrays of as many rows keep the same rows), and the row indices go beside it as
+    <name>_rows.npy."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    total = sum(t.numel() * np.dtype(dt).itemsize for _, t, dt in arrays)
+    frac = min(1.0, DUMP_LIMIT / float(world) / max(total, 1))
+    for name, t, dt in arrays:
+        rows = t.shape[0]
+        keep = rows if frac >= 1.0 else max(1, int(rows * frac))
+        if keep < rows:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows, keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            np.save(os.path.join(path, name + suffix + "_rows.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, name + suffix + ".npy"), t.cpu().numpy().astype(dt))
 
 
 AUDIO_KINDS = {0: "two tones + noise floor (tonal: a wrong start state survives thousands of units -- the hard case)",
@@ -431,6 +460,12 @@ def _main():
     ap.add_argument("--no-config-secondaries", action="store_true",
                     help="default run only: skip the other BASELINE configs (sbs_v3 share, xacd, strcd) and the RCCL world-size-1 self-test that "
                          "are run as subprocesses after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the parity check against the CPU oracle, the CPU baseline, the in-order kernel timing, the "
+                         "secondary figures and the other BASELINE configs.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of the rows of a larger output)")
     args = ap.parse_args()
     preset = dict(PRESETS[args.config or "sbs_v2"])
     if args.workload and args.workload != preset["workload"]:          # --workload alone keeps its round-2 meaning
@@ -543,6 +578,12 @@ def _main():
             ev[s_][1].record(streams[0])
     _barrier(args, dist, local_rank)
     elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs:
+        # the output buffers the launches cycle over (one per batch, or per stream), each as the last launch into it left it: with
+        # --launches-per-step >= their number (the default), all of them from the last step.  Row r = buffer r // n, frame r % n
+        nbuf = nb if ns == 1 else ns
+        _dump_outputs(args.dump_outputs, [("bitstream", torch.cat(d_outs[:nbuf]), np.float32), ("frame_results", torch.cat(d_ress[:nbuf]), np.float64)],
+                      rank, world)
 
     kernel_ms = [a.elapsed_time(b) / (lps if per_step else 1) for a, b in ev]      # per launch
     kstat = _stats(kernel_ms)
@@ -553,7 +594,8 @@ def _main():
     if ns > 1:      # launches overlap: a launch's own duration says little, the aggregate rate is what the GPU sustains
         achieved_local = alg_bytes * args.steps * lps / elapsed_local / 1e9
     overlapped = None
-    if lanes > 1:
+    in_order = lanes > 1 and args.full          # the in-order kernel timing below takes launches of its own: --full only
+    if in_order:
         # With two launch lanes consecutive launches overlap, and a step's event time / its launches is a launch's SHARE of the
         # GPU's time, not its duration.  The roofline block describes the KERNEL: its duration is measured right here, live, with
         # HIP events around the same launches in strict stream order (one lane: every launch waits for the one before) -- the
@@ -590,7 +632,7 @@ def _main():
     parity = None
     cpu_baseline = None
     secondary = None
-    if rank == 0:
+    if rank == 0 and args.full:
         import oracle_lib as O
         per = max(1, min(args.check_frames, n * len(ress)) // len(ress))
         ok, checked = True, 0
@@ -625,7 +667,7 @@ def _main():
     # what actually bounds the kernel: VALU issue.  A wave64 VALU instruction holds its SIMD's issue slot for 4 cycles;
     # instructions per launch come from the same committed PMC pass as the traffic (SQ_INSTS_VALU).
     issue = None
-    if pmc and pmc.get("valu_insts_per_launch") and not getattr(args, "share_gpu", False):      # (ranks sharing one GPU: a rank's kernel time is not the GPU's)
+    if pmc and pmc.get("valu_insts_per_launch") and not getattr(args, "share_gpu", False) and (lanes == 1 or in_order):      # (ranks sharing one GPU: a rank's kernel time is not the GPU's)
         simds, clock_ghz = 256 * 4, 2.4
         eff_ms = kstat["mean"] if ns == 1 else elapsed_local * 1e3 / (args.steps * lps)     # (several contexts: their launches' share of the wall clock; launch lanes: kstat is the in-order kernel duration)
         slots = simds * clock_ghz * 1e9 / 4.0 * (eff_ms * 1e-3)
@@ -665,8 +707,8 @@ def _main():
                        "frames_per_gpu_per_launch": n, "launches_per_step": lps, "distinct_batches": nb, "width": w, "height": h,
                        "frame_max_size": budget, "budget_cycle": cycle,
                        "secondary_summary": sec_summary,
-                       "in_order_frames_per_sec": round(n / (kstat["mean"] * 1e-3), 1) if ns == 1 else None,
-                       "in_order_note": "every launch waiting for the one before (one launch lane): n / roofline.kernel_ms; `value` is the two-lane rate" if lanes > 1 else None,
+                       "in_order_frames_per_sec": round(n / (kstat["mean"] * 1e-3), 1) if ns == 1 and (lanes == 1 or in_order) else None,
+                       "in_order_note": "every launch waiting for the one before (one launch lane): n / roofline.kernel_ms; `value` is the two-lane rate" if in_order else None,
                        "parallelism": "frames sharded x%d (contiguous ranges per rank), no data-path collective" % world,
                        "kernel_shape": {"groups_per_cu": geo.groups_per_cu, "wavefronts_per_group": geo.wavefronts_per_group,
                                         "image_tile_bytes": geo.image_tile_bytes, "frames_in_flight": geo.frames_in_flight},
@@ -682,10 +724,12 @@ def _main():
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
                          "frac_overlapped": overlapped["frac"] if overlapped else None, "traffic": traffic,
                          "traffic_source": traffic_src, "traffic_key": wl_key, "kernel_ms": kstat["mean"], "kernel_ms_stats": kstat,
-                         "launches_timed": (kstat.get("launches") if lanes > 1 else args.steps * lps),
+                         "launches_timed": (kstat.get("launches") if in_order else args.steps * lps),
                          "kernel_ms_method": ("strict stream order (one launch lane), measured after the timed region: one HIP event pair per block of %d back-to-back "
-                                              "launches, / %d; stats over 5 blocks" % (min(lps, 400), min(lps, 400))) if lanes > 1 else
-                                             (("one HIP event pair per step of %d back-to-back launches, / %d; stats over steps" % (lps, lps)) if per_step else "one HIP event pair per launch"),
+                                              "launches, / %d; stats over 5 blocks" % (min(lps, 400), min(lps, 400))) if in_order else
+                                             (("one HIP event pair per step of %d back-to-back launches, / %d; stats over steps%s" % (lps, lps, (
+                                                 " (two launch lanes: a launch's share of the GPU's time, not its duration; the in-order duration with --full)"
+                                                 if lanes > 1 else ""))) if per_step else "one HIP event pair per launch"),
                          "algorithmic_bytes_per_launch": alg_bytes, "issue": issue, "overlapped": overlapped,
                          **({"note": "launches of %d contexts overlap: achieved = algorithmic bytes of all launches / elapsed; kernel_ms are "
                                      "per-launch durations while sharing the GPU" % ns} if ns > 1 else {})},
@@ -1048,7 +1092,7 @@ def _secondary_configs(args):
     for name, cmd in jobs:
         t0 = time.perf_counter()
         try:
-            cmd = cmd + ["--detail-file", os.path.join(ddir, "bench_detail_child_%s.json" % name)]
+            cmd = cmd + ["--full", "--detail-file", os.path.join(ddir, "bench_detail_child_%s.json" % name)]
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
             line = None
             for ln in reversed(r.stdout.strip().splitlines()):
@@ -1125,34 +1169,38 @@ def bench_xacd(args):
         outs, passes = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:       # this rank's sectors of every channel, channel after channel
+        _dump_outputs(args.dump_outputs, [("xa_sectors", torch.cat(outs), np.float32)], rank, world)
     per_rank = _gather_ranks(dist, xdev, [elapsed, float(sec_cnt)])
     elapsed = max(r[0] for r in per_rank)                   # max over ranks
     # ---- the dominant kernel, live: HIP events around the speculate launch (adpcm_chunks_kernel<false, ..>) and around the verify
-    #      passes of a few further steps (psxhip_adpcm_session_set_timing: the events are on the session's own stream, inside the call)
+    #      passes of a few further steps (psxhip_adpcm_session_set_timing: the events are on the session's own stream, inside the call); --full only
     spec_ms, verify_ms = [], []
-    try:
-        sess.set_timing(True)
-        for _ in range(3):
-            step()
-            a_, b_ = sess.last_timing()
-            spec_ms.append(a_)
-            verify_ms.append(b_)
-        sess.set_timing(False)
-    except Exception:
-        pass
+    if args.full:
+        try:
+            sess.set_timing(True)
+            for _ in range(3):
+                step()
+                a_, b_ = sess.last_timing()
+                spec_ms.append(a_)
+                verify_ms.append(b_)
+            sess.set_timing(False)
+        except Exception:
+            pass
 
     parity = None
     cpu_baseline = None
     if rank == 0:
-        import oracle_lib as O
-        k = min(sec_cnt, 40)
-        x = pcm[0][:(k * sps + 4032) * 2].cpu().numpy() if sec_cnt * sps >= k * sps + 4032 else np.concatenate(
-            [pcm[0].cpu().numpy(), np.zeros(8064, np.int16)])
-        os_ = O.XaSettings(1, 1, 37800, 4, 1, 0)
-        want, _ = O.xa_encode(os_, x, k * sps, lba=0)
-        got = outs[0][:k].cpu().numpy().reshape(-1)
-        parity = {"sectors_checked": int(k), "bit_exact": bool(np.array_equal(got, want))}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            import oracle_lib as O
+            k = min(sec_cnt, 40)
+            x = pcm[0][:(k * sps + 4032) * 2].cpu().numpy() if sec_cnt * sps >= k * sps + 4032 else np.concatenate(
+                [pcm[0].cpu().numpy(), np.zeros(8064, np.int16)])
+            os_ = O.XaSettings(1, 1, 37800, 4, 1, 0)
+            want, _ = O.xa_encode(os_, x, k * sps, lba=0)
+            got = outs[0][:k].cpu().numpy().reshape(-1)
+            parity = {"sectors_checked": int(k), "bit_exact": bool(np.array_equal(got, want))}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu_baseline = _cpu_baseline_xa(args.seed, args.cpu_seconds)
         total_sectors = n_sectors * n_ch * args.steps
         value = total_sectors / elapsed
@@ -1242,11 +1290,13 @@ def bench_strcd(args):
         _, p2 = mux.encode_device(s, d_frames, d_pcm, d_out=d_out)
     _barrier(args, dist, local_rank)
     elapsed_local = time.perf_counter() - t0
+    if args.dump_outputs:       # the sectors of every stream, stream after stream
+        _dump_outputs(args.dump_outputs, [("str_sectors", d_out.reshape(-1, p.sector_size), np.float32)], rank, world)
     per_rank = _gather_ranks(dist, xdev, [elapsed_local, float(p.n_sectors * S * args.steps), float(p2.quant_scale_sum)])
     elapsed = max(r[0] for r in per_rank)
+    steps_only = args.steps_only or not args.full
     if rank == 0:
         import hashlib
-        import oracle_lib as O
         # ---- legs (untimed): the video leg alone (the same frames, no audio track), one stream alone, the host-buffer entry point
         legs = {}
 
@@ -1262,8 +1312,8 @@ def bench_strcd(args):
             m.close()
             return dt, o
         try:
-            if args.steps_only:
-                raise RuntimeError("skipped (--steps-only: every launch of the process belongs to a whole step, for the counter passes)")
+            if steps_only:
+                raise RuntimeError("skipped (--steps-only or no --full: every launch of the process belongs to a whole step)")
             s_v = strmux.settings(fmt=strmux.FORMAT_STRCD, codec=0, width=w, height=h, fps_num=15, fps_den=1, cd_speed=2, channels=0)
             dt_v, _ = timed_dev(s_v, d_frames, None, 20)
             pv = strmux.plan(s_v, n, 0)
@@ -1291,8 +1341,8 @@ def bench_strcd(args):
         frames0 = d_frames[0].cpu().numpy()
         pcm0 = d_pcm[0].cpu().numpy()
         try:
-            if args.steps_only:
-                raise RuntimeError("skipped (--steps-only)")
+            if steps_only:
+                raise RuntimeError("skipped (--steps-only or no --full)")
             sectors = np.zeros((p.n_sectors, p.sector_size), np.uint8)
             for _ in range(3):
                 strmux.encode(s, frames0, pcm0, device=local_rank, out=sectors)
@@ -1308,19 +1358,19 @@ def bench_strcd(args):
             legs["host_buffers_one_stream"] = {"error": repr(e)}
         # parity on a prefix: the reference's sector loop (tests/str_reference_loop.py over the oracle) on the first frames and
         # their share of the audio -- a complete little stream with its own tail -- through the DEVICE path
-        import str_reference_loop as R
         k = min(24, n)
         pk = pcm0[:2 * 2016 * 30]
-        if args.steps_only:
+        if steps_only:
             parity = None
         else:
+            import str_reference_loop as R
             sub, _ = mux.encode_device(s, d_frames[0, :k].contiguous(), torch.from_numpy(pk).to(dev))
             sub = sub.cpu().numpy()[0]
             osub, _, _ = R.encode_file_str(7, 0, w, h, 15, 1, 2, frames0[:k], pk)
             parity = {"sectors_checked": int(osub.shape[0]), "bit_exact": bool(sub.shape == osub.shape and np.array_equal(sub, osub)),
                       "streams_equal_host_path": legs.get("host_buffers_one_stream", {}).get("equals_device_path")}
         cpu_baseline = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             ref = os.path.join(ROOT, "oracle", "_ref", "libpsxav_ref.so")
             one = _run_cpu_bench(["str", 1, args.cpu_seconds * 0.6, args.seed] + ([ref] if os.path.exists(ref) else []))
             if one:

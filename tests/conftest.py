@@ -35,12 +35,3 @@ def oracle():
     oracle_lib.lib()
     return oracle_lib
 
-
-REFERENCE_ROOT = "/root/reference"
-
-
-@pytest.fixture(scope="session")
-def reference_root():
-    if not os.path.isdir(REFERENCE_ROOT):
-        pytest.skip("reference tree not present (GPU box)")
-    return REFERENCE_ROOT

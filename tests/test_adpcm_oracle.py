@@ -1,6 +1,6 @@
 """ADPCM restatement (oracle/adpcm_oracle.c) pinned two ways: against the reference's own libpsxav compiled
-unchanged (oracle/_ref, when present) and against tests/golden/adpcm_ref.npz, which was generated from that
-library by tests/golden/make_adpcm_golden.py.  Also the semantics the GPU search relies on."""
+unchanged (oracle/_ref, when present) and against tests/golden/adpcm_ref.npz and reference_cases.npz, which were
+generated from that library by tests/golden/make_adpcm_golden.py and make_reference_cases_golden.py.  Also the semantics the GPU search relies on."""
 import ctypes as C
 import hashlib
 import os
@@ -11,6 +11,7 @@ import pytest
 import oracle_lib as O
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "adpcm_ref.npz")
+CASES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_cases.npz")
 
 
 def sha(a):
@@ -90,32 +91,39 @@ def test_xa_golden_from_reference():
 
 
 def test_against_live_reference_build():
-    if O.ref() is None:
-        pytest.skip("oracle/_ref not built")
+    """the restatement against the reference's own build on random cases: live when oracle/_ref is present, and always against
+    that build's answers for the same cases recorded in tests/golden/reference_cases.npz (make_reference_cases_golden.py)"""
+    g = np.load(CASES)
+    R = O.ref()
     rng = np.random.default_rng(1)
     for trial in range(40):
         kind = int(rng.integers(0, 6))
         n = int(rng.integers(1, 3000))
         pcm = O.synth_pcm(int(rng.integers(1, 1 << 30)), trial, int(rng.integers(0, 1 << 20)), n, kind)
         a, sa = O.spu_encode(pcm)
-        b, sb = O.ref_spu_encode(pcm)
-        assert np.array_equal(a, b) and (sa.prev1, sa.prev2) == (sb.prev1, sb.prev2)
+        assert sha(a) == g["live_spu%d_sha" % trial].tobytes() and [sa.prev1, sa.prev2] == g["live_spu%d_state" % trial].tolist(), trial
+        if R is not None:
+            b, sb = O.ref_spu_encode(pcm)
+            assert np.array_equal(a, b) and (sa.prev1, sa.prev2) == (sb.prev1, sb.prev2)
     for trial in range(24):
         s = O.XaSettings(trial & 1, (trial >> 1) & 1, 37800 if trial & 4 else 18900, 8 if trial & 8 else 4, trial, trial * 3)
         n = int(rng.integers(1, 9000))
         kind = int(rng.integers(0, 6))
         pcm = stereo_pad(kind, n, trial) if s.stereo else mono_pad(kind, n, trial)
         a, sa = O.xa_encode(s, pcm, n, lba=trial * 1000)
-        b, sb = O.ref_xa_encode(s, pcm, n, lba=trial * 1000)
-        assert np.array_equal(a, b), trial
+        assert a.size == int(g["live_xa%d_len" % trial][0]) and sha(a) == g["live_xa%d_sha" % trial].tobytes(), trial
+        if R is not None:
+            b, sb = O.ref_xa_encode(s, pcm, n, lba=trial * 1000)
+            assert np.array_equal(a, b), trial
     # size helpers
-    R = O.ref()
     for trial in range(16):
         s = O.XaSettings(trial & 1, (trial >> 1) & 1, 37800 if trial & 4 else 18900, 8 if trial & 8 else 4, 0, 0)
-        rs = O.ref_settings(s)
-        assert O.lib().orc_xa_samples_per_sector(s) == R.psx_audio_xa_get_samples_per_sector(rs)
-        assert O.lib().orc_xa_sector_size(s) == R.psx_audio_xa_get_buffer_size_per_sector(rs)
-        assert O.lib().orc_xa_sector_interleave(s) == R.psx_audio_xa_get_sector_interleave(rs)
+        mine = [O.lib().orc_xa_samples_per_sector(s), O.lib().orc_xa_sector_size(s), O.lib().orc_xa_sector_interleave(s)]
+        assert mine == g["live_xa_size_helpers"][trial].tolist(), trial
+        if R is not None:
+            rs = O.ref_settings(s)
+            assert mine == [R.psx_audio_xa_get_samples_per_sector(rs), R.psx_audio_xa_get_buffer_size_per_sector(rs),
+                            R.psx_audio_xa_get_sector_interleave(rs)]
 
 
 def test_state_carry_across_calls():

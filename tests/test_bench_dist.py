@@ -51,7 +51,7 @@ PRESET_ARGS = {
 def test_rccl_leg_at_world_size_1_under_torchrun(preset):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), BENCH, "--gpus", "1", "--force-dist", "--dist-backend", "nccl", "--config", preset,
-           "--steps", "2", "--warmup", "1", "--no-secondary", "--no-cpu-baseline"] + PRESET_ARGS[preset]
+           "--steps", "2", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"] + PRESET_ARGS[preset]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
     line = _last_json(r.stdout)
     assert r.returncode == 0 and line is not None, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
@@ -71,7 +71,7 @@ def test_two_ranks_sharing_the_one_gpu_all_four_presets(preset):
     the rank arithmetic (contiguous shares, strong / weak scaling), the gathered per-rank counters, the max-over-ranks time and, for
     xacd, the time-shard protocol (final states all-gathered, second rank re-verified from its predecessor's truth)."""
     cmd = [sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--share-gpu", "--config", preset, "--steps", "2", "--warmup", "1",
-           "--no-secondary", "--no-cpu-baseline"] + PRESET_ARGS[preset]
+           "--full", "--no-secondary", "--no-cpu-baseline"] + PRESET_ARGS[preset]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     line = _last_json(r.stdout)
     assert r.returncode == 0 and line is not None, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
@@ -101,7 +101,7 @@ def test_forced_group_without_torchrun_sets_up_its_own_rendezvous():
 def test_c_abi_device_list_leg_of_the_bench_line():
     """the leg a single process runs over ALL visible devices of a multi-GPU node (psxhip_mdec_multi_* with one host thread, context
     and pinned staging pair per device), forced here onto the list 0,0: both schedules byte-equal to device 0 alone"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "1", "--warmup", "1", "--launches-per-step", "8", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "1", "--warmup", "1", "--launches-per-step", "8", "--full", "--no-cpu-baseline",
                         "--no-config-secondaries", "--device-list", "0,0"], env=_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     line = _last_json(r.stdout)
     assert r.returncode == 0 and line, (r.stdout[-2000:], r.stderr[-2000:])
@@ -140,10 +140,10 @@ REQUIRED_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per
 
 @pytest.mark.gpu
 def test_the_driver_command_prints_one_parsable_line_under_8_kb():
-    """`python bench.py --gpus 1 --steps K --warmup W` exactly as the driver runs it (all children included): the LAST line of stdout is
+    """`python bench.py --gpus 1 --steps K --warmup W --full` (all children included): the LAST line of stdout is
     the record, it parses, it is under 8 KB (the driver keeps an 8 KB tail; round 5's 36 KB line was lost), and it carries `roofline`
     and `cpu_baseline` for the headline and every BASELINE config as a {value, unit, frac, bit_exact} child."""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu-seconds", "3"], env=_env(), capture_output=True,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "3"], env=_env(), capture_output=True,
                        text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     last = r.stdout.strip().splitlines()[-1]
@@ -168,6 +168,37 @@ def test_the_driver_command_prints_one_parsable_line_under_8_kb():
 
 
 @pytest.mark.gpu
+def test_plain_run_is_the_timed_steps_and_dumps_the_last_step(tmp_path):
+    """without --full: the headline keys, no parity / CPU baseline / children; --dump-outputs writes the last step's bitstreams and frame
+    results as float .npy files under 64 MB (one seeded sample of rows for both), and the sampled frames are the ones the oracle encodes"""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--launches-per-step", "8",
+                        "--dump-outputs", str(out)], env=_env(), capture_output=True, text=True, timeout=600, cwd=ROOT)
+    line = _last_json(r.stdout)
+    assert r.returncode == 0 and line and "error" not in line, (r.stdout[-2000:], r.stderr[-2000:])
+    assert line["metric"] == "bs_v2_320x240_frames_per_sec" and line["unit"] == "frames/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "int32" and line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["cpu_baseline"] is None and line["parity"] is None and line["config"]["secondary_summary"] is None
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["bitstream.npy", "bitstream_rows.npy", "frame_results.npy", "frame_results_rows.npy"], files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    bs, rows, res, res_rows = (np.load(out / f) for f in files)
+    assert np.array_equal(rows, res_rows) and 0 < rows.size < 4000           # 4000 frames x 8192 bytes as float32 is over the limit: one sample for both
+    assert bs.dtype == np.float32 and res.dtype == np.float64 and res.shape == (rows.size, 4) and bs.shape == (rows.size, 8192)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import oracle_lib as O
+    from psxavenc_amd import synth
+    # row r = batch r // 1000 (drawn with seed 1 + batch), frame r % 1000
+    for r_ in rows.astype(np.int64)[:: max(1, rows.size // 6)]:
+        b, i = divmod(int(r_), 1000)
+        fr = synth.frames_device(320, 240, 1 + b, i, 1, 4, device=0).cpu().numpy()
+        want, want_res, rc = O.mdec_encode(0, 320, 240, fr, 8192)
+        k = int(np.searchsorted(rows, r_))
+        assert rc == 0 and np.array_equal(bs[k].astype(np.uint8), want[0]) and np.array_equal(res[k].astype(np.int32), want_res[0]), r_
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("preset", ["sbs_v2", "xacd"])
 def test_two_ranks_on_two_distinct_gpus_over_rccl(preset):
     """RCCL at world size 2 over DISTINCT devices -- only where the lease has two GPUs (skipped on the one-GPU boxes); the line carries
@@ -175,7 +206,7 @@ def test_two_ranks_on_two_distinct_gpus_over_rccl(preset):
     import torch
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible")
-    cmd = [sys.executable, BENCH, "--gpus", "2", "--config", preset, "--steps", "2", "--warmup", "1", "--no-secondary", "--no-cpu-baseline"] + PRESET_ARGS[preset]
+    cmd = [sys.executable, BENCH, "--gpus", "2", "--config", preset, "--steps", "2", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"] + PRESET_ARGS[preset]
     r = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900, cwd=ROOT)
     line = _last_json(r.stdout)
     assert r.returncode == 0 and line is not None and "error" not in line, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])

@@ -9,7 +9,7 @@ for i in 1 2; do
     [ "$path" != cur ] && lib="$PWD/$path"
     for wl in "a4:--amp 4 --launches-per-step 400" "a8:--amp 8 --launches-per-step 200" "v3:--config sbs_v3 --total-frames 1250 --launches-per-step 40"; do
       w=${wl%%:*}; args=${wl#*:}
-      PSXAV_HIP_LIB=$lib python bench.py --steps 4 --warmup 2 --lanes 1 --no-secondary --no-cpu-baseline $args > $O/ab_${tag}_${name}_${w}_$i.json 2> $O/ab_${tag}_${name}_${w}_$i.err
+      PSXAV_HIP_LIB=$lib python bench.py --full --steps 4 --warmup 2 --lanes 1 --no-secondary --no-cpu-baseline $args > $O/ab_${tag}_${name}_${w}_$i.json 2> $O/ab_${tag}_${name}_${w}_$i.err
       python - <<PY
 import json
 try:

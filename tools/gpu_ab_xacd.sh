@@ -8,7 +8,7 @@ for i in 1 2; do
     [ "$path" != cur ] && lib="$PWD/$path"
     for wl in "xacd:--config xacd --steps 6" "strcd:--config strcd --steps 60"; do
       w=${wl%%:*}; args=${wl#*:}
-      PSXAV_HIP_LIB=$lib python bench.py --warmup 2 --no-secondary --no-cpu-baseline $args > $O/abx_${name}_${w}_$i.json 2> $O/abx_${name}_${w}_$i.err
+      PSXAV_HIP_LIB=$lib python bench.py --full --warmup 2 --no-secondary --no-cpu-baseline $args > $O/abx_${name}_${w}_$i.json 2> $O/abx_${name}_${w}_$i.err
       python - <<PY
 import json
 try:

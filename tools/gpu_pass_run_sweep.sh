@@ -7,9 +7,9 @@ for g in 1 2 3 5; do
   export PSXHIP_MDEC_PASS_RUN=$g
   for wl in "a4:--amp 4 --launches-per-step 400" "a8:--amp 8 --launches-per-step 200" "v3:--config sbs_v3 --total-frames 1250 --launches-per-step 40"; do
     w=${wl%%:*}; args=${wl#*:}
-    python bench.py --steps 4 --warmup 2 --lanes 1 --no-secondary --no-cpu-baseline $args > $O/pr_${g}_$w.json 2>/dev/null
+    python bench.py --full --steps 4 --warmup 2 --lanes 1 --no-secondary --no-cpu-baseline $args > $O/pr_${g}_$w.json 2>/dev/null
     out=$O/pr_pmc_${g}_$w; rm -rf $out; mkdir -p $out
-    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out -o r -- python bench.py --steps 2 --warmup 1 --launches-per-step 16 --lanes 1 --no-cpu-baseline --no-secondary $args > $out/log 2>&1
+    rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out -o r -- python bench.py --full --steps 2 --warmup 1 --launches-per-step 16 --lanes 1 --no-cpu-baseline --no-secondary $args > $out/log 2>&1
     f=$(python tools/rocpd_summary.py $(find $out -name '*.db') 2>/dev/null | grep "mdec_encode_frames" | grep FETCH_SIZE | awk '{print $NF}')
     python - <<PY
 import json

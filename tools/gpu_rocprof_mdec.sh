@@ -14,8 +14,8 @@ mkdir -p $out
 # same workload (counter collection serialises the kernels)
 # --lanes 1: every launch waits for the one before, so a kernel's span in the trace IS its duration (bench.py's default overlaps
 # consecutive launches of its one context; its roofline block measures the in-order duration live, which is what this must agree with)
-full="python bench.py --lanes 1 --launches-per-step 400 --no-cpu-baseline --no-secondary $*"
-cmd="python bench.py --lanes 1 --steps 2 --warmup 1 --launches-per-step 16 --no-cpu-baseline --no-secondary $*"
+full="python bench.py --full --lanes 1 --launches-per-step 400 --no-cpu-baseline --no-secondary $*"
+cmd="python bench.py --full --lanes 1 --steps 2 --warmup 1 --launches-per-step 16 --no-cpu-baseline --no-secondary $*"
 rocprofv3 --kernel-trace --stats -d $out/kt -o r -- $full > $out/kt.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/fetch -o r -- $cmd > $out/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/write -o r -- $cmd > $out/write.log 2>&1

@@ -6,8 +6,8 @@ export TMPDIR=/tmp
 run() {   # name, lib, env
   name=$1; lib=$2; shift 2
   out=gpurun_out/v3t_$name; mkdir -p $out
-  cmd="python bench.py --config sbs_v3 --total-frames 1250 --steps 2 --warmup 1 --launches-per-step 8 --lanes 1 --no-cpu-baseline --no-secondary"
-  env "$@" PSXAV_HIP_LIB=$lib python bench.py --config sbs_v3 --total-frames 1250 --steps 4 --warmup 2 --launches-per-step 40 --lanes 1 --no-cpu-baseline --no-secondary > $out/bench.json 2> $out/bench.err
+  cmd="python bench.py --full --config sbs_v3 --total-frames 1250 --steps 2 --warmup 1 --launches-per-step 8 --lanes 1 --no-cpu-baseline --no-secondary"
+  env "$@" PSXAV_HIP_LIB=$lib python bench.py --full --config sbs_v3 --total-frames 1250 --steps 4 --warmup 2 --launches-per-step 40 --lanes 1 --no-cpu-baseline --no-secondary > $out/bench.json 2> $out/bench.err
   env "$@" PSXAV_HIP_LIB=$lib rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $out/fetch -o r -- $cmd > $out/fetch.log 2>&1
   env "$@" PSXAV_HIP_LIB=$lib rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $out/write -o r -- $cmd > $out/write.log 2>&1
   env "$@" PSXAV_HIP_LIB=$lib rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum --kernel-trace -d $out/tcc -o r -- $cmd > $out/tcc.log 2>&1

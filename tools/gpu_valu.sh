@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 out=gpurun_out/valu_$tag
 rm -rf $out; mkdir -p $out
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD --kernel-trace -d $out -o r -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --launches-per-step 1 "$@" > $out/log 2>&1
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VMEM_RD --kernel-trace -d $out -o r -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --launches-per-step 1 "$@" > $out/log 2>&1
 python - $out $mbs $tag <<'PY'
 import sqlite3, sys, glob
 db = glob.glob(sys.argv[1] + "/**/*.db", recursive=True)[0]

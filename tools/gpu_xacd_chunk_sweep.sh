@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 for cw in "4096 128" "3797 128" "3797 64" "2048 128" "1899 128" "1899 64" "1899 32" "1266 64" "950 64" "950 32"; do
   set -- $cw
-  PSXHIP_ADPCM_CHUNK=$1 PSXHIP_ADPCM_WARM=$2 python bench.py --config xacd --steps 6 --warmup 2 --no-secondary --no-cpu-baseline > $O/xsw_$1_$2.json 2> $O/xsw_$1_$2.err
+  PSXHIP_ADPCM_CHUNK=$1 PSXHIP_ADPCM_WARM=$2 python bench.py --full --config xacd --steps 6 --warmup 2 --no-secondary --no-cpu-baseline > $O/xsw_$1_$2.json 2> $O/xsw_$1_$2.err
   python - <<PY
 import json
 try:

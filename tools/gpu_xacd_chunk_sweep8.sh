@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out; mkdir -p $O
 for cw in "1024 32" "768 32" "512 32" "512 64" "384 32" "256 32" "238 32" "238 64" "128 16"; do
   set -- $cw
-  PSXHIP_ADPCM_CHUNK=$1 PSXHIP_ADPCM_WARM=$2 python bench.py --config xacd --audio-seconds 450 --steps 10 --warmup 2 --no-secondary --no-cpu-baseline > $O/xs8_$1_$2.json 2> $O/xs8_$1_$2.err
+  PSXHIP_ADPCM_CHUNK=$1 PSXHIP_ADPCM_WARM=$2 python bench.py --full --config xacd --audio-seconds 450 --steps 10 --warmup 2 --no-secondary --no-cpu-baseline > $O/xs8_$1_$2.json 2> $O/xs8_$1_$2.err
   python - <<PY
 import json
 try:
