@@ -39,11 +39,16 @@ const char *psxhip_version(void);
 
 /* what encode_frame_bs leaves in mdec_encoder_state_t (psxavenc/mdec.c:719-736) */
 typedef struct {
-	int32_t quant_scale;         /* 1..63; 64 = no scale fits (bytes_used = 0 then) */
+	int32_t quant_scale;         /* 1..63; 64 = no scale fits (bytes_used = 0 then); PSXHIP_MDEC_QS_RELEASED: see below */
 	int32_t bytes_used;          /* bitstream bytes incl. the 8-byte header, rounded up to 4 */
 	int32_t blocks_used;         /* MDEC command word count */
 	int32_t uncomp_hwords_used;  /* rounded up to 64 */
 } psxhip_mdec_result_t;
+
+/* quant_scale of a frame the split kernel's watchdog released (psxhip_mdec_encode_frames_device / _batches_device only): its
+ * workgroups did not all arrive in time, so nothing is known about the frame -- the row is zero, the other fields are 0.  It is
+ * not "does not fit": encode the frame again (the host-buffer entry points do that by themselves, through the frame kernel). */
+#define PSXHIP_MDEC_QS_RELEASED 65
 
 typedef struct psxhip_mdec_ctx psxhip_mdec_ctx_t;
 
@@ -69,8 +74,9 @@ void psxhip_mdec_destroy(psxhip_mdec_ctx_t *ctx);
  * Launches of at most 12 frames (PSXHIP_MDEC_SPLIT_MAX) cut every frame across many workgroups (csrc/mdec_split.inc: the
  * reference's call pattern is ONE frame per call, psxavenc/filefmt.c:641-647) -- same bytes, same results, same ordering rules.  Such
  * launches of one process are ordered one behind the other per device; a frame whose workgroups could not all become resident
- * within 0.2 s (another PROCESS holding the device's compute units) comes back with quant_scale 64 and is counted by
- * psxhip_mdec_watchdog -- the host-buffer one-frame call takes such a frame again through the one-workgroup kernel by itself. */
+ * within 0.2 s (another PROCESS holding the device's compute units) comes back with quant_scale PSXHIP_MDEC_QS_RELEASED and a zero
+ * row, and is counted by psxhip_mdec_watchdog.  The host-buffer entry points (psxhip_mdec_encode_frames_host, encode_frame_bs,
+ * the STR and multi-device calls) encode such a frame again through the one-workgroup kernel and return its exact bytes. */
 int psxhip_mdec_encode_frames_device(psxhip_mdec_ctx_t *ctx, const uint8_t *d_frames, size_t frame_stride,
                                      int n_frames, const int32_t *d_frame_max_sizes, int uniform_max_size,
                                      uint8_t *d_out, size_t out_stride, psxhip_mdec_result_t *d_results,
@@ -113,13 +119,15 @@ int psxhip_mdec_encode_batches_device(psxhip_mdec_ctx_t *ctx, const psxhip_mdec_
 int psxhip_mdec_set_lanes(psxhip_mdec_ctx_t *ctx, int lanes);
 /* order `stream` behind every launch of the context issued so far (a no-op with one lane) */
 int psxhip_mdec_fence(psxhip_mdec_ctx_t *ctx, void *stream);
-/* Waits for the context's launches and returns, in *lost, how often the retry queue's watchdog gave a frame up (a workgroup that
- * reserved a queue slot never filled it within about a second: a faulted or preempted workgroup).  0 on a healthy device --
- * anything else means some launch's results are incomplete.  Never reset. */
+/* Waits for the context's launches and returns, in *lost, how often a watchdog gave a frame up: the retry queue's (a workgroup that
+ * reserved a queue slot never filled it within about a second: a faulted or preempted workgroup -- that launch's results are
+ * incomplete), and the split kernel's (a frame whose workgroups did not all arrive within 0.2 s: reported as
+ * PSXHIP_MDEC_QS_RELEASED, or encoded again by the host-buffer entry points).  Each released frame counts once.  Never reset. */
 int psxhip_mdec_watchdog(psxhip_mdec_ctx_t *ctx, unsigned *lost);
 
 /* Same, host buffers: H2D, kernel, D2H, synchronise.  frame_max_sizes may be NULL (uniform).
- * Returns PSXHIP_ENOFIT if any frame could not be fitted (its result has quant_scale 64).
+ * Returns PSXHIP_ENOFIT if any frame could not be fitted (its result has quant_scale 64).  A frame the split kernel's watchdog
+ * released is encoded again through the frame kernel: it never comes back as 64 or PSXHIP_MDEC_QS_RELEASED here.
  * The batch moves in chunks over two streams (the copies of one chunk overlap the kernel of the next).  Pageable `frames`
  * / `out` go through pinned staging buffers (a multi-threaded CPU copy per chunk); buffers that are page-locked --
  * hipHostMalloc, hipHostRegister or psxhip_host_register() below -- are read and written by DMA directly. */

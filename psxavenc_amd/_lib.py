@@ -11,6 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PSXAV_HIP_LIB") or os.path.join(_HERE, "libpsxav_hip.so")
 
 PSXHIP_OK, PSXHIP_EINVAL, PSXHIP_EDEVICE, PSXHIP_ENOMEM, PSXHIP_ENOFIT = 0, -1, -2, -3, -4
+# quant_scale of a frame the split kernel's watchdog released (device entry points only; include/psxav_hip.h)
+PSXHIP_MDEC_QS_RELEASED = 65
 
 
 class MdecResult(C.Structure):

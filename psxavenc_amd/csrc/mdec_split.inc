@@ -33,6 +33,20 @@
 //
 // Results are identical to the frame kernel's and to the reference's loop by construction: same DCT forms (fdct8_pk), same
 // quantiser (quant_mag), same tables, and the search is the reference's own ascending scan.
+//
+// Released frames.  A wait that outlasts the patience gives the frame up: its row is zero and its quant_scale PSXHIP_MDEC_QS_RELEASED
+// (not 64: that is "fits nowhere"), counted once in psxhip_mdec_watchdog; the host-buffer entry points encode it again with the frame
+// kernel.  Groups of a released frame may still come and publish into the workspace, so every group counts itself out and the last
+// one out of a released frame zeroes the whole workspace (see `leave` below): no word of one launch reaches the next.
+//
+// Test switches (read when a context is created, psxhip_api.cpp):
+//   PSXHIP_MDEC_SPLIT_WITHHOLD=frame:segment[:launches[:residue]] -- for the context's first `launches` split launches (default 1),
+//     every other group of frame `frame` reads segment `segment`'s slots, DC words and done word as never there, without waiting
+//     (segment: 0 .. segs - 1, `mid` = segs / 2, negative = from the end: -1 is the finisher's own).  The withheld group publishes
+//     nothing and leaves; with `residue` it publishes its round-0 sums, its DC words and done = 2 and leaves, and the finisher does not
+//     zero that segment's words -- what a group that comes after the finisher leaves, without timing.
+//   PSXHIP_MDEC_SPLIT_PATIENCE=<ticks of the 100 MHz clock> -- the patience of every wait (default 20 000 000: 0.2 s).  A short one
+//     makes real releases and real late groups on an idle GPU; it only shortens waits.
 
 namespace {
 
@@ -43,7 +57,7 @@ constexpr int kSplitRounds = 5;              // 8 + 4 x 16 >= 63
 constexpr int kSplitMbMaxBits = 6 * (24 + 63 * 22 + 2);
 constexpr int kSplitWbufWords = (kSplitMbMaxBits + 10 + 31) / 32 + 2;
 static_assert(kSplitWbufWords * 4 >= 6 * kTileStride * 2, "a wavefront's transpose tile fits its stream buffer");
-constexpr unsigned long long kSplitPatience = 20000000ull;    // ticks of the 100 MHz wall clock a rendezvous waits: 0.2 s
+constexpr unsigned long long kSplitPatience = 20000000ull;    // ticks of the 100 MHz wall clock a rendezvous waits: 0.2 s (default)
 
 struct SplitJob {
     const uint8_t* frames;
@@ -64,6 +78,8 @@ struct SplitJob {
     unsigned* done_flag;             // page-locked host word the last group stores done_seq into once the frame's row and result are written (one-frame calls), or NULL
     unsigned done_seq;
     unsigned long long* dbg;         // diagnostics (PSXHIP_MDEC_SPLIT_DBG): [group][8] wall-clock stamps at the phase boundaries, or NULL
+    unsigned long long patience;     // ticks a rendezvous waits (kSplitPatience; PSXHIP_MDEC_SPLIT_PATIENCE)
+    int wh_frame, wh_seg, wh_residue;   // PSXHIP_MDEC_SPLIT_WITHHOLD (tests): segment wh_seg of frame wh_frame never arrives (wh_seg < 0: off)
 };
 
 __device__ __forceinline__ unsigned ld_agent(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -71,14 +87,14 @@ __device__ __forceinline__ unsigned long long ld_agent64(const unsigned long lon
 
 // A published word (never zero), read when it is there: device-scope loads until it reads non-zero.  Returns 0 when the watchdog gives up.
 template <typename T>
-__device__ __forceinline__ T split_await(const T* p) {
+__device__ __forceinline__ T split_await(const T* p, unsigned long long patience) {
     T v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (v) return v;
     const unsigned long long t0 = wall_clock64();
     for (;;) {
         __builtin_amdgcn_s_sleep(2);
         v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v || wall_clock64() - t0 > kSplitPatience) return v;
+        if (v || wall_clock64() - t0 > patience) return v;
     }
 }
 // a word of the frame's row or result: written through to wherever the row lives (HBM, or the page-locked host block of a one-frame
@@ -136,7 +152,7 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
     int16_t* T = (int16_t*)wbuf;                // (the DCT's transpose tiles, dead before the first stream is built)
     int16_t* dcv = (int16_t*)(smem + o);        if (CODEC != 0) o += ((size_t)nmb * 6 * 2 + 15) & ~15;
     int* dc_fn = (int*)(smem + o);
-    enum { SC_LBITS = 0, SC_LNNZ = 16, SC_TOT = 32, SC_NNZ = 48, SC_PRE = 64, SC_DEAD = 80, SC_ANSWER, SC_LAST, SC_SINK, SC_COUNT = 96 };
+    enum { SC_LBITS = 0, SC_LNNZ = 16, SC_TOT = 32, SC_NNZ = 48, SC_PRE = 64, SC_DEAD = 80, SC_ANSWER, SC_LAST, SC_SINK, SC_EXIT, SC_COUNT = 96 };
 
     // ---- workspace of this frame
     unsigned char* wsf = job.ws + (size_t)f * job.ws_stride;
@@ -144,7 +160,40 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
     unsigned* dcw = (unsigned*)(wsf + job.ws_dcq);                               // v3: [macroblock][3] two biased DC terms per word
     unsigned* img = (unsigned*)(wsf + job.ws_img);
     unsigned* done = (unsigned*)(wsf + job.ws_done);                             // [segment] 1: done, 2: done, released by the watchdog
+    // PSXHIP_MDEC_SPLIT_WITHHOLD (tests): every other group of the frame reads the withheld segment's words as never there, without
+    // waiting; the withheld group itself publishes nothing (or, with `residue`, its round-0 sums, its DC words and done = 2) and leaves
+    const bool wh = job.wh_seg >= 0 && f == job.wh_frame, withheld = wh && seg == job.wh_seg;
+    auto hidden = [&](int g) { return wh && !withheld && g == job.wh_seg; };
+    const unsigned long long pat = job.patience;
+    unsigned* exits = (unsigned*)wsf;                                            // groups of the frame that have left | 0x10000: released
 
+    // Leaving.  A frame the finisher released may still have groups to come: they publish sums, DC words and done words, and OR image
+    // bits, into a workspace the next launch reads as its own arrivals.  So every group counts itself out (the finisher adds 0x10000 when
+    // it released the frame), and the last one out of a released frame returns the whole workspace to zero.  Split launches of a device
+    // run one behind the other, so nothing of this launch is left when the next one starts.  (A frame that was not released was
+    // tidied by its finisher, behind every group's done word: the last one out only resets the count.)
+    auto leave = [&](unsigned inc) {
+        split_drain();
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned now = __hip_atomic_fetch_add(exits, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + inc;
+            sc[SC_EXIT] = (now & 0xFFFFu) == (unsigned)segs ? (now >> 16 ? 2 : 1) : 0;
+        }
+        __syncthreads();
+        const int last = sc[SC_EXIT];
+        if (last == 2) {
+            for (int i = tid; i < job.img_words; i += kSplitThreads) __hip_atomic_store(&img[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int r = 0; r < kSplitRounds; r++)
+                for (int i = tid; i < segs * kSplitRound; i += kSplitThreads)
+                    __hip_atomic_store(&slots[((size_t)r * nmb) * kSplitRound + i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (CODEC != 0)
+                for (int i = tid; i < nmb * 3; i += kSplitThreads) __hip_atomic_store(&dcw[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int i = tid; i < segs; i += kSplitThreads) __hip_atomic_store(&done[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (last && tid == 0) __hip_atomic_store(exits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+
+    if (withheld && !job.wh_residue && seg != segs - 1) { leave(1u); return; }
     int max_size = job.max_sizes ? job.max_sizes[f] : job.uniform_max_size;
     const bool bad_budget = max_size < 8 || max_size > job.max_frame_size || (size_t)max_size > job.out_stride;
     if (bad_budget) max_size = 8;
@@ -241,7 +290,7 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
         // ---- v3: every group needs every block's DC term (mdec.c:454-479): all of them read, then the three chains here
         bool got = true;
         for (int i = tid; i < nmb * 3; i += kSplitThreads) {
-            const unsigned v = split_await(&dcw[i]);
+            const unsigned v = hidden(i / 3 / M) ? 0u : split_await(&dcw[i], pat);
             got = got && v != 0u;
             dcv[2 * i] = (int16_t)((int)(v & 0xFFFFu) - 513);
             dcv[2 * i + 1] = (int16_t)((int)(v >> 16) - 513);
@@ -434,6 +483,7 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
             __hip_atomic_store(&rslots[seg * kSplitRound + tid], (unsigned long long)(unsigned)sc[SC_LBITS + tid] | ((unsigned long long)(unsigned)sc[SC_LNNZ + tid] << 32),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (round == 0) stamp(2);
+        if (withheld) { alive = false; break; }          // (a withheld group leaves behind its round-0 sums, waiting for nobody)
         // While the sums travel: every wavefront codes its macroblock at ONE candidate scale into its own buffer -- the first wavefronts of a
         // macroblock at cbase, cbase + 1 -- at the previous call's answer (neighbouring frames of a video mostly agree), or around
         // what this segment's own bits would mean for the frame.  A hit leaves only the placing for after the answer.
@@ -466,7 +516,7 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
             bool got = true;
             if (sl < cnt && base + 1 + sl <= 63)
                 for (int g = aw >> 4; g < segs; g += n_aw / kSplitRound) {
-                    const unsigned long long v = split_await(&rslots[g * kSplitRound + sl]);
+                    const unsigned long long v = hidden(g) ? 0ull : split_await(&rslots[g * kSplitRound + sl], pat);
                     got = got && v != 0ull;
                     tot += (int)(unsigned)v;
                     nnz += (int)(unsigned)(v >> 32);
@@ -529,10 +579,10 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
     split_drain();
     __syncthreads();
     if (tid == 0) __hip_atomic_store(&done[seg], alive ? 1u : 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (seg != segs - 1) return;
+    if (seg != segs - 1) { leave(1u); return; }
     {
         bool bad = false;
-        for (int i = tid; i < segs; i += kSplitThreads) bad = bad || split_await(&done[i]) != 1u;      // (0: the watchdog; 2: a group it released)
+        for (int i = tid; i < segs; i += kSplitThreads) bad = bad || (hidden(i) ? 0u : split_await(&done[i], pat)) != 1u;      // (0: the watchdog; 2: a group it released)
         if (bad) sc[SC_DEAD] = 2;
     }
     __syncthreads();
@@ -542,12 +592,14 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
     const bool tripped = sc[SC_DEAD] != 0;
     if (tripped && tid == 0) atomicAdd(job.lost, 1u);
     if (!answer || tripped) {
-        // nothing fits (the reference asserts, mdec.c:723) -- or the watchdog gave up: zero output, flag the result
+        // nothing fits (the reference asserts, mdec.c:723): quant_scale 64 -- or the watchdog gave up: PSXHIP_MDEC_QS_RELEASED, which
+        // says nothing about the frame (the host paths encode it again with the frame kernel).  Zero output either way.
         if (!bad_budget) {
             for (int i = tid; i < (max_size >> 2); i += kSplitThreads) row_store(&o32[i], 0u);
             if (tid < (max_size & 3)) outp[(max_size & ~3) + tid] = 0;
         }
-        if (tid < 4) row_store((uint32_t*)&job.results[f] + tid, tid == 0 ? 64u : 0u);
+        const uint32_t qs = tripped && !bad_budget ? (uint32_t)PSXHIP_MDEC_QS_RELEASED : 64u;
+        if (tid < 4) row_store((uint32_t*)&job.results[f] + tid, tid == 0 ? qs : 0u);
     } else {
         const int sl = answer - abase - 1;
         const int total_bits = sc[SC_TOT + sl] + 10, nnz = sc[SC_NNZ + sl];
@@ -582,14 +634,19 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
     stamp(6);
     // the workspace goes back to zero for the next launch: device-scope stores (the next launch's device-scope loads and ORs are
     // served at the memory side; a plain store could sit in this XCD's L2)
+    // (WITHHOLD with `residue`: the withheld segment's words are left as a group that comes late leaves them)
+    const int keep = wh && job.wh_residue ? job.wh_seg : -1;
     for (int i = tid; i < job.img_words; i += kSplitThreads) __hip_atomic_store(&img[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int r = 0; r < rounds_used; r++)
         for (int i = tid; i < segs * kSplitRound; i += kSplitThreads)
-            __hip_atomic_store(&slots[((size_t)r * nmb) * kSplitRound + i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (i / kSplitRound != keep) __hip_atomic_store(&slots[((size_t)r * nmb) * kSplitRound + i], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (CODEC != 0)
-        for (int i = tid; i < nmb * 3; i += kSplitThreads) __hip_atomic_store(&dcw[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int i = tid; i < segs; i += kSplitThreads) __hip_atomic_store(&done[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = tid; i < nmb * 3; i += kSplitThreads)
+            if (i / 3 / M != keep) __hip_atomic_store(&dcw[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int i = tid; i < segs; i += kSplitThreads)
+        if (i != keep) __hip_atomic_store(&done[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     stamp(7);
+    leave(tripped ? 0x10001u : 1u);
 }
 
 }  // namespace
@@ -634,6 +691,8 @@ extern "C" hipError_t psxhip_mdec_split_launch(const psxhip_mdec_split_t* a) {
     job.lost = a->d_lost;
     job.dbg = a->d_dbg;
     job.done_flag = a->d_done_flag; job.done_seq = a->done_seq; job.hint = a->hint;
+    job.patience = a->patience ? a->patience : kSplitPatience;
+    job.wh_frame = a->wh_frame; job.wh_seg = a->wh_seg < a->geo.segs ? a->wh_seg : -1; job.wh_residue = a->wh_residue;
     const dim3 grid((unsigned)(a->geo.segs * a->n_frames)), block((unsigned)kSplitThreads);
     hipStream_t st = (hipStream_t)a->stream;
     switch (a->codec) {

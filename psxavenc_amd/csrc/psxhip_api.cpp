@@ -3,6 +3,7 @@
 // no CPU fallback: without a gfx950 device every entry point fails with PSXHIP_EDEVICE.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -141,6 +142,9 @@ struct psxhip_mdec_ctx {
     int split_max;                    // launches of at most this many frames take the split kernel (0: never)
     unsigned long long* d_split_dbg;  // diagnostics (PSXHIP_MDEC_SPLIT_DBG=1): phase stamps of the last split launch
     int split_dbg_groups;
+    unsigned long long split_patience;   // tests (PSXHIP_MDEC_SPLIT_PATIENCE): ticks a rendezvous waits (0: the kernel's default)
+    int wh_frame, wh_seg, wh_launches, wh_residue;   // tests (PSXHIP_MDEC_SPLIT_WITHHOLD): see mdec_split.inc; wh_launches = 0: off
+    long long split_launches;         // split launches of this context so far
     // diagnostics (PSXHIP_PERCALL_TRACE=1): where a one-frame call's host time goes, printed when the context is destroyed
     bool call_trace;
     double call_ns[6];                // copy in, stage-in launch, encode launch, wait, copy out, calls
@@ -306,6 +310,21 @@ extern "C" int psxhip_mdec_create(psxhip_mdec_ctx_t** out, int device, int codec
         c->split_max = 12;
         if (const char* e = getenv("PSXHIP_MDEC_SPLIT_MAX")) c->split_max = atoi(e);
         if (c->split_max > 64) c->split_max = 64;
+        // test switches (mdec_split.inc's header): a rendezvous' patience, and a segment that never arrives
+        if (const char* e = getenv("PSXHIP_MDEC_SPLIT_PATIENCE")) c->split_patience = strtoull(e, nullptr, 10);
+        if (const char* e = getenv("PSXHIP_MDEC_SPLIT_WITHHOLD")) {
+            // frame:segment[:launches[:residue]] -- segment: 0 .. segs - 1 (larger: the last), negative: from the end (-1: the
+            // finisher's own), "mid": segs / 2
+            char seg[16] = {0};
+            int fr = 0, launches = 1, residue = 0;
+            const int n = sscanf(e, "%d:%15[^:]:%d:%d", &fr, seg, &launches, &residue);
+            if (n >= 2 && fr >= 0 && launches > 0) {
+                c->wh_frame = fr;
+                c->wh_seg = strcmp(seg, "mid") == 0 ? INT_MIN : atoi(seg);
+                c->wh_launches = launches;
+                c->wh_residue = residue != 0;
+            }
+        }
         psxhip_mdec_split_geo_t g;
         if (c->split_max > 0 && psxhip_mdec_split_geometry(codec, width, height, max_frame_size, 1, c->n_cu, &g)) {
             c->split_ws_stride = g.ws_stride;
@@ -416,6 +435,14 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
             sp.d_dbg = c->d_split_dbg;
             c->split_dbg_groups = sp.geo.segs * n_frames;
             sp.stream = stream;
+            sp.patience = c->split_patience;
+            sp.wh_seg = -1;
+            if (c->split_launches++ < c->wh_launches) {
+                const int segs = sp.geo.segs, w = c->wh_seg;
+                sp.wh_frame = c->wh_frame;
+                sp.wh_seg = w == INT_MIN ? segs / 2 : (w < 0 ? (segs + w >= 0 ? segs + w : 0) : (w < segs ? w : segs - 1));
+                sp.wh_residue = c->wh_residue;
+            }
             static const bool no_gate = getenv("PSXHIP_NO_SPLIT_GATE") != nullptr;      // experiments only: what happens without the gate (tests/test_gpu_split_threads.py)
             if (no_gate) {
                 HIP_TRY(psxhip_mdec_split_launch(&sp), PSXHIP_EDEVICE);
@@ -607,6 +634,16 @@ extern "C" int psxhip_mdec_encode_batches_device(psxhip_mdec_ctx_t* c, const psx
     return PSXHIP_OK;
 }
 
+extern "C" int psxhip_mdec_encode_batches_frame_kernel(psxhip_mdec_ctx_t* c, const psxhip_mdec_batch_t* batches, int n_batches,
+                                                       size_t frame_stride, int uniform_max_size, size_t out_stride, void* stream) {
+    if (!c) return PSXHIP_EINVAL;
+    const int split_max = c->split_max;
+    c->split_max = 0;
+    const int rc = psxhip_mdec_encode_batches_device(c, batches, n_batches, frame_stride, uniform_max_size, out_stride, stream);
+    c->split_max = split_max;
+    return rc;
+}
+
 extern "C" int psxhip_mdec_encode_frames_device(psxhip_mdec_ctx_t* c, const uint8_t* d_frames, size_t frame_stride,
                                                 int n_frames, const int32_t* d_frame_max_sizes,
                                                 int uniform_max_size, uint8_t* d_out, size_t out_stride,
@@ -781,6 +818,7 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
                 c->h_call = nullptr;
                 c->call_disabled = true;
             } else {
+                memset(c->h_call, 0, fpad + opad + 64);          // (the done flag among it: a stale word equal to a call's number would end the wait early)
                 c->d_call = (uint8_t*)dp;
                 c->call_out_off = fpad;
                 c->call_res_off = fpad + opad;
@@ -859,9 +897,9 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
                 }
             }
             memcpy(results, c->h_call + c->call_res_off, sizeof(psxhip_mdec_result_t));
-            if (flagged && results[0].quant_scale >= 64) {
-                // "nothing fits" from the split kernel is also what a frame says whose groups the watchdog released (another process
-                // holding the CUs for 0.2 s): the frame kernel has the last word -- the reference aborts here, nobody waits for this
+            if (flagged && results[0].quant_scale == PSXHIP_MDEC_QS_RELEASED) {
+                // a frame whose groups the watchdog released (another process holding the CUs for 0.2 s): the frame kernel encodes it
+                // (the stream is waited for first: the split launch's last group may still be tidying the workspace)
                 HIP_TRY(hipStreamSynchronize(c->stream), PSXHIP_EDEVICE);
                 rc = mdec_launch_lane(c, 0, &bd, 1, (fsz + 3) & ~(size_t)3, one, dstride, c->stream, nullptr, 0, nullptr, nullptr, true);
                 if (rc) return rc;
@@ -969,6 +1007,16 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
         HIP_TRY(hipEventSynchronize(c->chunk_done[k & 1]), PSXHIP_EDEVICE);
         deliver(k);
     }
+    // frames the split kernel's watchdog released: again, one by one, through the frame kernel (rare: another process held the CUs)
+    for (int i = 0; i < n_frames; i++)
+        if (results[i].quant_scale == PSXHIP_MDEC_QS_RELEASED) {
+            const int split_max = c->split_max;
+            c->split_max = 0;
+            const int rc = psxhip_mdec_encode_frames_host_rows(c, frames + (size_t)i * fsz, 1, frame_max_sizes ? frame_max_sizes + i : nullptr,
+                                                               uniform_max_size, out + (size_t)i * out_stride, out_stride, results + i, max_size);
+            c->split_max = split_max;
+            if (rc && rc != PSXHIP_ENOFIT) return rc;
+        }
     for (int i = 0; i < n_frames; i++)
         if (results[i].quant_scale >= 64) {
             psxhip_set_error("frame %d does not fit %d bytes at any quant scale", i,

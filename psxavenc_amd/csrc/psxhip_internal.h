@@ -65,10 +65,15 @@ typedef struct {
 	unsigned int done_seq;
 	int hint;                           /* the answer of the context's previous one-frame call (0: none) */
 	void *stream;
+	unsigned long long patience;        /* ticks of the 100 MHz clock a rendezvous waits (0: the default, 0.2 s) */
+	int wh_frame, wh_seg, wh_residue;   /* tests (PSXHIP_MDEC_SPLIT_WITHHOLD): segment wh_seg (0 .. segs - 1; -1: none) of frame wh_frame never arrives */
 } psxhip_mdec_split_t;
 /* 1: the split kernel takes launches of n_frames frames of this geometry (g filled in), 0: it does not */
 int psxhip_mdec_split_geometry(int codec, int width, int height, int max_frame_size, int n_frames, int n_cu, psxhip_mdec_split_geo_t *g);
 hipError_t psxhip_mdec_split_launch(const psxhip_mdec_split_t *a);
+/* psxhip_mdec_encode_batches_device through the frame kernel only (frames the split kernel's watchdog released, encoded again) */
+int psxhip_mdec_encode_batches_frame_kernel(psxhip_mdec_ctx_t *ctx, const psxhip_mdec_batch_t *batches, int n_batches,
+                                            size_t frame_stride, int uniform_max_size, size_t out_stride, void *stream);
 
 size_t psxhip_mdec_lds_bytes(int nmb, int out_words, int stg_words, int large);
 int psxhip_mdec_threads_per_group(int large);

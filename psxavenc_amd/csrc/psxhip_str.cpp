@@ -638,6 +638,8 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     const size_t ostride = ((size_t)pl.pub.max_frame_size + 3) & ~(size_t)3;
 
     // ---- video: one batched launch over the frames of all streams, then the sector kernel, both on the caller's stream
+    psxhip_str_video_job_t vj;
+    memset(&vj, 0, sizeof vj);
     if (nf) {
         const int key[4] = {s->video_codec, s->video_width, s->video_height, pl.pub.max_frame_size};
         if (!d.mdec || memcmp(key, d.mdec_key, sizeof key) != 0) {
@@ -660,7 +662,6 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         }
         int rc = psxhip_mdec_encode_batches_device(d.mdec, batches.data(), (int)batches.size(), fsz, 0, ostride, S);
         if (rc) return rc;
-        psxhip_str_video_job_t vj;
         vj.d_bs = (const uint8_t*)d.d_bs;
         vj.bs_stride = ostride;
         vj.bs_stream_stride = ostride * (size_t)nf;
@@ -683,8 +684,6 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         DEV_TRY(hipMemcpyAsync(d.h_res, d.d_res, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
     } else if (d.n_vtab) {
         // no frame in the stream, but audio slots without samples: zero sectors (nothing reads a bitstream)
-        psxhip_str_video_job_t vj;
-        memset(&vj, 0, sizeof vj);
         vj.d_bs = (const uint8_t*)d.d_bs; vj.d_res = (const psxhip_mdec_result_t*)d.d_res; vj.d_tab = (const int32_t*)d.d_vtab;
         vj.n_entries = d.n_vtab; vj.n_streams = n_streams; vj.format = s->format; vj.sector_size = (int)ssz; vj.d_out = d_out;
         vj.out_stream_stride = out_stream_stride;
@@ -770,6 +769,30 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         DEV_TRY(hipStreamWaitEvent(S, d.ev_audio, 0), PSXHIP_EDEVICE);
     }
     DEV_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
+    if (nf) {
+        // frames the split kernel's watchdog released (another process held the CUs): encoded again through the frame kernel, and
+        // the video sectors built again over them
+        std::vector<psxhip_mdec_batch_t> again;
+        for (size_t i = 0; i < (size_t)nf * n_streams; i++)
+            if (d.h_res[i].quant_scale == PSXHIP_MDEC_QS_RELEASED) {
+                psxhip_mdec_batch_t b;
+                b.d_frames = d_frames + (i / (size_t)nf) * frames_stream_stride + (i % (size_t)nf) * fsz;
+                b.n_frames = 1;
+                b.reserved = 0;
+                b.d_frame_max_sizes = (const int32_t*)d.d_budgets + i;
+                b.d_out = (uint8_t*)d.d_bs + i * ostride;
+                b.d_results = (psxhip_mdec_result_t*)d.d_res + i;
+                again.push_back(b);
+            }
+        if (!again.empty()) {
+            int rc = psxhip_mdec_encode_batches_frame_kernel(d.mdec, again.data(), (int)again.size(), fsz, 0, ostride, S);
+            if (rc) return rc;
+            rc = psxhip_str_video_sectors_launch(device, &vj, S);
+            if (rc) return rc;
+            DEV_TRY(hipMemcpyAsync(d.h_res, d.d_res, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
+            DEV_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
+        }
+    }
     long long qsum = 0;
     for (size_t i = 0; i < (size_t)nf * n_streams; i++) {
         if (d.h_res[i].quant_scale >= 64) {

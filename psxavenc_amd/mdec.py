@@ -90,7 +90,9 @@ class MdecEncoder:
     # ---- batched device path (torch tensors on the encoder's device) -----------------------------
     def encode_frames_device(self, d_frames, frame_max_sizes, d_out=None, d_results=None, stream=None):
         """d_frames: uint8 CUDA tensor (n, frame_stride).  frame_max_sizes: int or int32 CUDA tensor (n,).
-        Returns (d_out (n, out_stride) uint8, d_results (n, 4) int32); asynchronous on the stream."""
+        Returns (d_out (n, out_stride) uint8, d_results (n, 4) int32); asynchronous on the stream.  A launch of at most 12
+        frames may report a frame as _lib.PSXHIP_MDEC_QS_RELEASED (65, zero row): the split kernel's watchdog gave it up -- encode it
+        again (encode_frames_host does that by itself); 64 is "fits no scale", as in the reference."""
         assert torch is not None and d_frames.is_cuda and d_frames.dtype == torch.uint8 and d_frames.dim() == 2
         n, fstride = d_frames.shape
         if isinstance(frame_max_sizes, int):
@@ -149,7 +151,8 @@ class MdecEncoder:
         _lib.check(L.psxhip_mdec_fence(self._h, st.cuda_stream))
 
     def watchdog(self):
-        """psxhip_mdec_watchdog: frames the retry queue's watchdog gave up (0 on a healthy device); synchronises"""
+        """psxhip_mdec_watchdog: frames a watchdog gave up -- the retry queue's, or the split kernel's releases, each released
+        frame once (0 on a healthy device); synchronises"""
         L = _lib.lib()
         L.psxhip_mdec_watchdog.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
         lost = C.c_uint(0)
