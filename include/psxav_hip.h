@@ -492,6 +492,39 @@ int psxhip_scaler_convert_host(psxhip_scaler_t *s, const uint8_t *src, int n_fra
  * the number of output positions, *taps per position; fills left[n] / coef[n * taps] when both are given (cap elements) */
 int psxhip_scaler_filter(const psxhip_scaler_t *s, int which, int *taps, int32_t *left, int16_t *coef, int cap);
 
+/* ---------------------------------------------------------------- audio front-end: resample + remix ---- */
+
+/* What the reference leaves to FFmpeg's libswresample (psxavenc/decoding.c:215-254: swr_alloc_set_opts2 to S16 at the target
+ * rate, mono or stereo; :370-406: swr_convert once per decoded packet): decoded PCM of any rate and layout -> interleaved int16
+ * at the target rate and channel count, on the device, written where the ADPCM and STR kernels read their input.  The
+ * arithmetic is this library's own ("psxhip audio front-end v1"): int16 conversion, a Q14 channel
+ * matrix at the source rate, a Kaiser-windowed sinc polyphase filter with Q15 taps and libswresample's default parameters.
+ * PARITY WITH libswresample IS UNPINNED.  A handle keeps the filter history: a stream cut into any number of calls gives the
+ * same bytes as one call. */
+enum { PSXHIP_PCM_S16 = 0, PSXHIP_PCM_S16P = 1, PSXHIP_PCM_S32 = 2, PSXHIP_PCM_S32P = 3, PSXHIP_PCM_F32 = 4, PSXHIP_PCM_F32P = 5 };
+typedef struct psxhip_resampler psxhip_resampler_t;
+/* pure host, no device needed: the table the rates imply (returns P, or < 0; *taps = T; fills coef[P*T] when cap allows).
+ * Equal rates are a bypass: P = 1, T = 0. */
+int psxhip_resampler_design(int src_rate, int dst_rate, int *phases, int *taps, int16_t *coef, int cap);
+/* pure host: outputs per channel of a call adding n_in samples to a stream that has consumed `consumed` (not flushed); < 0 on
+ * bad arguments */
+int64_t psxhip_resampler_output_count(int src_rate, int dst_rate, int64_t consumed, int64_t n_in, int flush);
+/* rates 1 000 .. 384 000 Hz, at most 16x either way; 1 .. 8 channels.  mix: dst_channels x src_channels, Q14, no row with
+ * sum |m| > 65535; NULL = the default for N -> N, 2 -> 1, 1 -> 2 and 6 -> 2 (5.1), PSXHIP_EINVAL for any other shape */
+int psxhip_resampler_create(psxhip_resampler_t **r, int device, int src_format, int src_channels, int src_rate,
+                            int dst_channels, int dst_rate, const int16_t *mix /* dst x src, Q14; NULL = default */);
+void psxhip_resampler_destroy(psxhip_resampler_t *r);
+void psxhip_resampler_reset(psxhip_resampler_t *r);
+/* src: 1 pointer (interleaved) or src_channels pointers (planar), device memory; d_dst: interleaved int16, room for
+ * output_count(...) * dst_channels; asynchronous on `stream`; calls on one handle are stream-ordered.  After a flush, calls
+ * return PSXHIP_EINVAL until psxhip_resampler_reset. */
+int psxhip_resampler_convert_device(psxhip_resampler_t *r, const void *const *src, int64_t n_in, int16_t *d_dst,
+                                    int64_t *n_out, int flush, void *stream);
+/* host buffers: H2D, kernel, D2H, synchronise (psxavenc's per-packet swr_convert call site); dst_cap in samples per channel */
+int psxhip_resampler_convert_host(psxhip_resampler_t *r, const void *const *src, int64_t n_in, int16_t *dst,
+                                  int64_t dst_cap, int64_t *n_out, int flush);
+const char *psxhip_resampler_kernel_rev(void);   /* "afe-k1.2": the key for profiles of this kernel */
+
 /* ---------------------------------------------------------------- synthetic inputs --------- */
 
 /* Integer-only generators (same function as oracle/synth.c) so benchmarks can fill HBM directly. */

@@ -137,6 +137,32 @@ void psxhip_adpcm_pick_chunking(long long total_units, int rows, int device, int
  * psxhip_str_encode_device ask the same function */
 int psxhip_adpcm_chunked_threshold(int n_chains);
 
+/* ... and with every change to the audio front-end kernel (audio_frontend_kernels.hip) */
+#define PSXHIP_AFE_KERNEL_REV "afe-k1.2"
+
+/* one launch of the audio front-end (audio_frontend_kernels.hip): n_out outputs of a stream, from the filter history and n_in
+ * new source samples.  Indices are relative to the launch's first new sample; history sample h of channel c is y[h - (T - 1)]. */
+#define PSXHIP_AFE_TILE 256                 /* outputs per tile = threads per workgroup */
+typedef struct {
+	const void *src[8];                 /* interleaved: src[0] only */
+	int fmt, sch, dch;
+	int bypass;                         /* equal rates: y copied, no filter, no history */
+	int64_t n_in, n_out;                /* n_in <= 2^28 (the host cuts longer calls); n_out up to 16x that: indices are int64 */
+	int64_t i0;                         /* input index of output 0 (>= -H) */
+	int r0;                             /* (its absolute index * M) mod L */
+	int L, M, P, T, H;
+	const int16_t *coef;                /* [P][T] Q15 taps, device memory */
+	int coef_lds;                       /* 1: the table is copied into LDS once per workgroup */
+	int span;                           /* int16 per channel per copy in LDS: >= (L - 1 + (TILE - 1) M) / L + T, even */
+	const int16_t *hist_in;             /* [dch][T - 1] */
+	int16_t *hist_out;                  /* [dch][T - 1], written by the launch (the last tile) */
+	int16_t *dst;                       /* [n_out][dch] */
+	int16_t mix[8][8];                  /* [dst][src] Q14 */
+} psxhip_afe_job_t;
+size_t psxhip_afe_lds_bytes(const psxhip_afe_job_t *j);
+hipError_t psxhip_afe_prepare(int dch, int coef_lds, size_t lds_bytes);
+hipError_t psxhip_afe_launch(const psxhip_afe_job_t *j, int grid, void *stream);
+
 void psxhip_set_error(const char *fmt, ...);
 
 #ifdef __cplusplus
