@@ -477,7 +477,8 @@ enum {
 typedef struct psxhip_scaler psxhip_scaler_t;
 /* src_full_range: YUV input only -- 0 = limited ("MPEG") range, expanded to the full range the encoder expects
  * (decoding.c:301-311 passes the stream's own range as the source range); RGB input is full range by definition.
- * dst_width / dst_height: multiples of 16 (mdec.c:601-602), at most 1024; shrinking by more than 16x is refused. */
+ * dst_width / dst_height: multiples of 16 (mdec.c:601-602), at most 1024; shrinking by more than 16x is refused, in any of the
+ * four filters (RGB chroma is filtered from full resolution to dst / 2: it shrinks twice as much as luma). */
 int psxhip_scaler_create(psxhip_scaler_t **s, int device, int src_format, int src_width, int src_height, int src_full_range,
                          int dst_width, int dst_height);
 void psxhip_scaler_destroy(psxhip_scaler_t *s);

@@ -583,10 +583,16 @@ extern "C" int psxhip_scaler_create(psxhip_scaler_t** out, int device, int src_f
     s->device = device; s->fmt = src_format; s->sw = src_width; s->sh = src_height; s->full_range = src_full_range;
     s->dw = dst_width; s->dh = dst_height;
     const int csw = yuv ? src_width / 2 : src_width, csh = yuv ? src_height / 2 : src_height;
-    if (!make_bank(src_width, dst_width, &s->h[0]) || !make_bank(src_height, dst_height, &s->h[1]) ||
-        !make_bank(csw, dst_width / 2, &s->h[2]) || !make_bank(csh, dst_height / 2, &s->h[3])) {
-        psxhip_set_error("psxhip_scaler_create: shrinking by more than 16x is not supported");
-        return PSXHIP_EINVAL;
+    {
+        // lh, lv, ch, cv: RGB chroma is filtered from full resolution to half the target, so its banks shrink twice as much
+        static const char* const names[4] = {"luma horizontal", "luma vertical", "chroma horizontal", "chroma vertical"};
+        const int from[4] = {src_width, src_height, csw, csh}, to[4] = {dst_width, dst_height, dst_width / 2, dst_height / 2};
+        for (int i = 0; i < 4; i++)
+            if (!make_bank(from[i], to[i], &s->h[i])) {
+                psxhip_set_error("psxhip_scaler_create: the %s filter (%d -> %d%s) shrinks by more than 16x, which is not supported",
+                                 names[i], from[i], to[i], (i >= 2 && !yuv) ? ": RGB chroma is filtered from full resolution" : "");
+                return PSXHIP_EINVAL;
+            }
     }
     s->src_bytes = yuv ? (size_t)src_width * src_height * 3 / 2 : (size_t)src_width * src_height * 3;
     ScalerJob& j = s->job;
@@ -598,10 +604,21 @@ extern "C" int psxhip_scaler_create(psxhip_scaler_t** out, int device, int src_f
     HIP_TRY(hipGetDeviceProperties(&prop, device), PSXHIP_EDEVICE);
     s->n_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     // tile: the largest of these whose LDS working set leaves room for at least two workgroups per CU
+    // (PSXHIP_SCALER_TILE=k, tests: only shapes[k], taken if one workgroup fits a CU -- every shape can be run on purpose)
     const int shapes[4][2] = {{64, 16}, {32, 16}, {32, 8}, {16, 8}};
+    int t_first = 0, t_last = 3;
+    const char* forced = getenv("PSXHIP_SCALER_TILE");
+    if (forced) {
+        const int k = atoi(forced);
+        if (k < 0 || k > 3) {
+            psxhip_set_error("psxhip_scaler_create: PSXHIP_SCALER_TILE=%s is not a tile shape (0..3)", forced);
+            return PSXHIP_EINVAL;
+        }
+        t_first = t_last = k;
+    }
     size_t need = 0;
     bool ok = false;
-    for (int t = 0; t < 4 && !ok; t++) {
+    for (int t = t_first; t <= t_last && !ok; t++) {
         const int TW = shapes[t][0], TH = shapes[t][1];
         // the largest source reach of any tile, from the tables
         auto reach = [](const HostBank& b, int n, int tile, int* lo_of_first, int* span) {
@@ -658,11 +675,16 @@ extern "C" int psxhip_scaler_create(psxhip_scaler_t** out, int device, int src_f
         const size_t v_words = (size_t)TH + TH / 2 + ((size_t)TH * s->h[1].taps + (size_t)(TH / 2) * s->h[3].taps + 1) / 2;      // one tile's vertical tables
         need = plane + 2 * cplane + 2 * ((size_t)reg_rows * TW + 2 * crows_cap * (TW / 2)) +
                8 * ((size_t)TW * s->h[0].taps4 + (size_t)(TW / 2) * s->h[2].taps4) + 4 * ((size_t)TW + TW / 2) + 4 * 2 * v_words + 16 * (((size_t)dst_height + TH - 1) / TH) + 16;
-        if (need * 2 <= (size_t)prop.maxSharedMemoryPerMultiProcessor || (t == 3 && need <= (size_t)prop.maxSharedMemoryPerMultiProcessor)) {
+        if (need * 2 <= (size_t)prop.maxSharedMemoryPerMultiProcessor || ((t == 3 || forced) && need <= (size_t)prop.maxSharedMemoryPerMultiProcessor)) {
             ok = true;
             j.TW = TW; j.TH = TH;
             j.reg_rows = reg_rows; j.reg_cols = reg_cols; j.creg_rows = creg_rows; j.creg_cols = creg_cols;
         }
+    }
+    if (!ok && forced) {
+        psxhip_set_error("psxhip_scaler_create: tile %dx%d (PSXHIP_SCALER_TILE=%d) needs %zu bytes of LDS, more than the %d of a compute unit",
+                         shapes[t_first][0], shapes[t_first][1], t_first, need, (int)prop.maxSharedMemoryPerMultiProcessor);
+        return PSXHIP_EINVAL;
     }
     if (!ok) {
         psxhip_set_error("psxhip_scaler_create: the filters' reach (%zu bytes of LDS per tile) does not fit a compute unit", need);

@@ -248,6 +248,13 @@ def scaler_filter(src, dst):
     return taps.value, left, coef[:dst * taps.value].reshape(dst, taps.value)
 
 
+def scaler_filter_accepts(src, dst):
+    """whether the specification has a filter bank for src -> dst (at most 64 taps: shrinking by at most 16x)"""
+    left = np.zeros(dst, np.int32)
+    coef = np.zeros(dst * 64, np.int16)
+    return lib().orc_scaler_filter(src, dst, None, left.ctypes.data_as(C.POINTER(C.c_int32)), ptr(coef, i16p), coef.size) == 0
+
+
 def scaler_convert(fmt, src_w, src_h, full_range, dst_w, dst_h, pictures):
     """pictures: (n, bytes per picture) uint8 -> (n, dst_w * dst_h * 3 / 2) NV21"""
     pictures = np.ascontiguousarray(pictures, dtype=np.uint8)

@@ -1,9 +1,12 @@
 """The CPU checker of the colour-conversion / scaling front-end (oracle/frontend_oracle.c) against what can
 be known without libswscale (parity with the reference's scaler is UNPINNED -- FFmpeg is absent): the filter bank's
 invariants, exact identities, and closeness to a double-precision bicubic + BT.601 full-range model.  Tolerances are the
-fixed-point format's: 14-bit coefficients, 15-bit intermediates."""
+fixed-point format's: 14-bit coefficients, 15-bit intermediates.  On hard content the statement is held to the float64 model of
+tests/scaler_model.py within a bound derived from each geometry's banks; impulses pin the banks' placement exactly."""
 import numpy as np
 import pytest
+
+import scaler_model as M
 
 
 def _cubic(x, B=0.0, Cc=0.6):
@@ -108,3 +111,75 @@ def test_limited_range_input_expands_to_full_range(oracle):
     pic = np.concatenate([np.full(w * h, 128, np.uint8), np.full(w * h // 4, 240, np.uint8), np.full(w * h // 4, 16, np.uint8)])
     out = oracle.scaler_convert(oracle.PIX_YUV420P, w, h, False, w, h, pic[None])[0]
     assert (out[w * h::2] <= 1).all() and (out[w * h + 1::2] >= 254).all()       # Cr from V = 16, Cb from U = 240
+
+
+# ---------------------------------------------------------------- hard content against the float64 model (tests/scaler_model.py)
+@pytest.mark.parametrize("fmt,sw,sh,full,dw,dh", M.TILE_GEOMETRIES + M.EXTREME_GEOMETRIES)
+def test_hard_content_within_the_derived_bound(oracle, fmt, sw, sh, full, dw, dh):
+    """the CPU statement against the real-valued model on content that drives every clamp: per plane within the bound the
+    geometry's own banks allow (scaler_model.plane_bound, derived, not fitted), and on noise unbiased to within 0.05 with a
+    mean error of a rounding (about 0.25): a wrong rounding constant moves both to about 0.5"""
+    bounds = M.convert_bounds(fmt, sw, sh, full, dw, dh, oracle.scaler_filter)
+    pics = M.hard_pictures(fmt, sw, sh, dw, dh, limited=not full, seed=sw * 7 + dh, kinds=M.kinds_for(sw, sh))
+    for name, pic in pics:
+        out = oracle.scaler_convert(fmt, sw, sh, full, dw, dh, pic[None])[0]
+        got, want = M.nv21_planes(out, dw, dh), M.model_convert(fmt, sw, sh, full, dw, dh, pic)
+        for plane, g, w, b in zip(("Y", "Cr", "Cb"), got, want, (bounds[0], bounds[1], bounds[1])):
+            err = np.abs(g - w).max()
+            assert err <= b, "%s, plane %s: max |err| %.3f over the bound %.3f" % (name, plane, err, b)
+        if name == "noise":
+            d = np.concatenate([(g - w).ravel() for g, w in zip(got, want)])
+            assert np.abs(d).mean() <= 0.30 and abs(d.mean()) <= 0.05, (np.abs(d).mean(), d.mean())
+
+
+def _impulse_spec(taps, left, coef, n_src, p):
+    """sum of the bank's coefficients that land on source sample p (edge replication), per output: int64"""
+    idx = np.clip(left[:, None].astype(np.int64) + np.arange(taps)[None, :], 0, n_src - 1)
+    return (coef.astype(np.int64) * (idx == p)).sum(axis=1)
+
+
+@pytest.mark.parametrize("sw,sh,dw,dh", [(4096, 256, 256, 16), (2, 2, 1024, 1024)])
+def test_impulse_response_is_the_bank(oracle, sw, sh, dw, dh):
+    """one sample of 255 in a black plane (Y, and V under it), at the first, middle and last column and row: every output byte
+    is the specification evaluated for that one sample from scaler_filter's bank -- a shifted `left`, or a tap applied to the
+    wrong source column, fails.  16x down: 64-tap banks; 2 -> 1024: `left` runs below 0 and past the end."""
+    lh, lv = oracle.scaler_filter(sw, dw), oracle.scaler_filter(sh, dh)
+    ch, cv = oracle.scaler_filter(sw // 2, dw // 2), oracle.scaler_filter(sh // 2, dh // 2)
+
+    def plane(hb, vb, n_w, n_h, p, q):
+        a = _impulse_spec(*hb, n_w, p)
+        b = _impulse_spec(*vb, n_h, q)
+        t = np.clip((255 * a) >> 7, 0, 32767)
+        return np.clip((b[:, None] * t[None, :] + (1 << 20)) >> 21, 0, 255)
+
+    for p in sorted({0, sw // 2, sw - 1}):
+        for q in sorted({0, sh // 2, sh - 1}):
+            y = np.zeros((sh, sw), np.uint8)
+            u = np.zeros((sh // 2, sw // 2), np.uint8)
+            v = np.zeros((sh // 2, sw // 2), np.uint8)
+            y[q, p] = 255
+            v[q // 2, p // 2] = 255
+            pic = np.concatenate([y.ravel(), u.ravel(), v.ravel()])
+            out = oracle.scaler_convert(oracle.PIX_YUV420P, sw, sh, True, dw, dh, pic[None])[0]
+            gy, gcr, gcb = M.nv21_planes(out, dw, dh)
+            assert np.array_equal(gy, plane(lh, lv, sw, sh, p, q)), (p, q)
+            assert np.array_equal(gcr, plane(ch, cv, sw // 2, sh // 2, p // 2, q // 2)), (p, q)
+            assert (gcb == 0).all()
+
+
+def test_acceptance_is_sixteen_times_per_bank(oracle):
+    """a bank exists exactly when its 16.16 increment is at most 16 (64 taps); RGB chroma is filtered from full resolution to
+    half the target, so RGB 2560x1440 -> 320x240 is accepted (chroma 2560 -> 160: exactly 16x) and 2561x1441 -> 320x240 is
+    refused by its chroma bank although luma shrinks only 8x"""
+    for src, dst in ((1024, 64), (1025, 64), (1039, 64), (1040, 64), (1041, 64), (2560, 160), (2561, 160), (16384, 1024), (16385, 1024),
+                     (16384, 1023), (4096, 256), (4104, 256), (4105, 256)):
+        assert oracle.scaler_filter_accepts(src, dst) == (M.xinc(src, dst) <= 16 * 65536), (src, dst)
+
+    def banks(fmt, sw, sh, dw, dh):
+        csw, csh = (sw, sh) if fmt == 0 else (sw // 2, sh // 2)
+        return [(sw, dw), (sh, dh), (csw, dw // 2), (csh, dh // 2)]
+
+    assert all(oracle.scaler_filter_accepts(s, d) for s, d in banks(0, 2560, 1440, 320, 240))
+    refused = [k for k, (s, d) in enumerate(banks(0, 2561, 1441, 320, 240)) if not oracle.scaler_filter_accepts(s, d)]
+    assert refused == [2], refused        # the chroma horizontal bank alone
+    assert M.xinc(2561, 320) <= 8 * 65536 + 65536 // 8
