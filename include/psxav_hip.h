@@ -39,7 +39,7 @@ const char *psxhip_version(void);
 
 /* what encode_frame_bs leaves in mdec_encoder_state_t (psxavenc/mdec.c:719-736) */
 typedef struct {
-	int32_t quant_scale;         /* 1..63; 64 = no scale fits (bytes_used = 0 then); PSXHIP_MDEC_QS_RELEASED: see below */
+	int32_t quant_scale;         /* 1..63; 64 = no scale fits (bytes_used = 0 then, and the frame_max_size bytes of its row are zero); PSXHIP_MDEC_QS_RELEASED: see below */
 	int32_t bytes_used;          /* bitstream bytes incl. the 8-byte header, rounded up to 4 */
 	int32_t blocks_used;         /* MDEC command word count */
 	int32_t uncomp_hwords_used;  /* rounded up to 64 */

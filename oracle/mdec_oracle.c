@@ -346,6 +346,28 @@ int orc_mdec_encode_frame(int codec, int w, int h, const uint8_t *nv21, int fram
 	return 0;
 }
 
+/* One rate-control attempt at ONE scale, into a buffer no frame can outgrow: the bytes that scale needs (8 + 2 x words, before the
+ * round-up to 4) and the attempt's status (1 = fit, as always there; ORC_MDEC_EDCRANGE = undefined DC code).  tests/ draw their exact
+ * budgets from this curve: scale s fits a budget b exactly when need(s) <= b - (b & 1). */
+int orc_mdec_need_at_scale(int codec, int w, int h, const uint8_t *nv21, int scale, int *bytes_needed) {
+	if (w <= 0 || h <= 0 || (w % 16) || (h % 16) || scale < 1 || scale > 63) return ORC_MDEC_EINVAL;
+	const int nmb = (w / 16) * (h / 16);
+	/* per block at most 63 escapes of 22 bits, a 10-bit DC code and the 2-bit end mark; then the 10-bit end of frame */
+	const int cap = 8 + 2 * ((nmb * 6 * (63 * 22 + 12) + 10 + 15) / 16) + 4;
+	int16_t *coefs = malloc((size_t)nmb * 6 * 64 * sizeof(int16_t));
+	uint8_t *out = malloc((size_t)cap);
+	int used = 0, hwords = 0, rc = ORC_MDEC_EINVAL;
+	if (coefs && out) {
+		orc_mdec_frame_to_coefs(w, h, nv21, coefs);
+		rc = attempt(codec, w, h, coefs, scale, out, cap, &used, &hwords);
+		if (rc < 0) rc = ORC_MDEC_EDCRANGE;
+	}
+	free(coefs);
+	free(out);
+	if (rc == 1 && bytes_needed) *bytes_needed = used;
+	return rc;
+}
+
 int orc_mdec_encode_frames(int codec, int w, int h, const uint8_t *frames, int n_frames,
                            const int *frame_max_sizes, int out_stride, uint8_t *out,
                            orc_mdec_result_t *res) {

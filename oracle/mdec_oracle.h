@@ -35,6 +35,7 @@ int orc_mdec_encode_frame(int codec, int w, int h, const uint8_t *nv21, int fram
 int orc_mdec_encode_frames(int codec, int w, int h, const uint8_t *frames, int n_frames,
                            const int *frame_max_sizes, int out_stride, uint8_t *out,
                            orc_mdec_result_t *res);
+int orc_mdec_need_at_scale(int codec, int w, int h, const uint8_t *nv21, int scale, int *bytes_needed);   /* one attempt, unbounded buffer */
 int orc_mdec_encode_sector_str(orc_str_state_t *st, int codec, int w, int h, int format,
                                uint16_t str_video_id, const uint8_t *video_frames, uint8_t *output);
 

@@ -81,6 +81,7 @@ def lib():
         L.orc_mdec_encode_frame.argtypes = [C.c_int, C.c_int, C.c_int, u8p, C.c_int, u8p, C.POINTER(MdecResult)]
         L.orc_mdec_encode_frames.argtypes = [C.c_int, C.c_int, C.c_int, u8p, C.c_int, intp, C.c_int, u8p,
                                              C.POINTER(MdecResult)]
+        L.orc_mdec_need_at_scale.argtypes = [C.c_int, C.c_int, C.c_int, u8p, C.c_int, intp]
         L.orc_mdec_frame_to_coefs.argtypes = [C.c_int, C.c_int, u8p, i16p]
         L.orc_fdct_islow8.argtypes = [i16p]
         L.orc_mdec_ac_code.restype = C.c_uint32
@@ -166,6 +167,20 @@ def mdec_encode(codec, w, h, frames, budgets, stride=None):
     rc = lib().orc_mdec_encode_frames(codec, w, h, ptr(frames, u8p), n, ptr(budgets, intp), stride, ptr(out, u8p), res)
     r = np.array([[x.quant_scale, x.bytes_used, x.blocks_used, x.uncomp_hwords_used] for x in res], dtype=np.int32)
     return out, r, rc
+
+
+def mdec_need(codec, w, h, frame):
+    """need[s], s = 1..63 (need[0] = 0): the bytes the frame's stream takes at scale s, 8 + 2 x words before the round-up to 4
+    -- one attempt of the encoder's own loop per scale, into a buffer that cannot overflow.  Scale s fits a budget b exactly when
+    need[s] <= b - (b & 1)."""
+    frame = np.ascontiguousarray(frame, dtype=np.uint8)
+    need = np.zeros(64, np.int64)
+    v = C.c_int()
+    for s in range(1, 64):
+        rc = lib().orc_mdec_need_at_scale(codec, w, h, ptr(frame, u8p), s, C.byref(v))
+        assert rc == 1, (rc, s)
+        need[s] = v.value
+    return need
 
 
 def mdec_coefs(w, h, frame):

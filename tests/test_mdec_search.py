@@ -1,6 +1,11 @@
 """CPU test of the MDEC rate-control search policy (psxavenc_amd/csrc/mdec_search.h): whatever the bits(scale)
 curve looks like -- monotone, bumpy, with or without the lower-bound proof being available -- the search must
-return the FIRST scale that fits (the reference's ascending loop, psxavenc/mdec.c:663-723) and terminate."""
+return the FIRST scale that fits (the reference's ascending loop, psxavenc/mdec.c:663-723) and terminate.
+
+The curves here are synthetic and their lower bound is valid by construction.  The same policy on the REAL curves of non-monotone
+frames, with the deficits the kernels read, at every exact budget: tests/test_mdec_bound.py
+(test_search_policy_returns_the_first_fit_on_real_non_monotone_curves); that the bound itself is valid: the same file; the kernels
+on those frames: tests/test_gpu_mdec_thresholds.py."""
 import ctypes as C
 import os
 import subprocess

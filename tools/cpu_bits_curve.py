@@ -1,50 +1,16 @@
 #!/usr/bin/env python3
 """CPU study tool (uses the oracle, never the product): AC bits(scale) and the refinement lower bound of synthetic
-frames, fed through the search-policy simulator (tests/cpu/search_sim.cpp)."""
+frames, fed through the search-policy simulator (tests/cpu/search_sim.cpp).  The curve code is tests/mdec_hard_content.py's, which
+tests/test_mdec_bound.py holds to the oracle; that test also runs the simulator on non-monotone frames."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import oracle_lib as O
-
-
-def luts():
-    src = open(os.path.join(ROOT, "psxavenc_amd/csrc/bs_vlc_lut.h")).read()
-    m = re.search(r"bs_ac_len16_lut\[\d+\] = \{(.*?)\};", src, re.S)
-    v = np.array([int(x, 16) for x in m.group(1).replace("\n", " ").split(",") if x.strip()]).reshape(42, 63)
-    q = re.search(r"bs_quant_zz\[64\] = \{(.*?)\};", src, re.S)
-    quant = np.array([int(x) for x in q.group(1).replace("\n", " ").split(",") if x.strip()])
-    z = re.search(r"bs_zagzig\[64\] = \{(.*?)\};", src, re.S)
-    zz = np.array([int(x) for x in z.group(1).replace("\n", " ").split(",") if x.strip()])
-    return v & 0xFF, v >> 8, quant, zz
-
-
-def curves(w, h, frame, scales=range(1, 64)):
-    """AC bits and deficits per scale for one frame: returns (tb_ac[64], def[64])"""
-    lens, defs, quant, zz = luts()
-    co = O.mdec_coefs(w, h, frame).reshape(-1, 64)[:, zz].astype(np.int64)     # blocks x 64, zig-zag order
-    co[:, 0] = 0
-    tb = np.zeros(64, np.int64)
-    df = np.zeros(64, np.int64)
-    a = np.abs(co)
-    for s in scales:
-        d = quant * s
-        q = (2 * a + d) // (2 * d)
-        nz = q != 0
-        nz[:, 0] = False
-        # run before each nonzero: position - previous nonzero position - 1 (previous = 0 for the DC slot)
-        pos = np.where(nz, np.arange(64)[None, :], 0)
-        prev = np.maximum.accumulate(pos, axis=1)
-        prevpos = np.concatenate([np.zeros((co.shape[0], 1), np.int64), prev[:, :-1]], axis=1)
-        run = np.arange(64)[None, :] - prevpos - 1
-        lv = np.minimum(q, 41)
-        tb[s] = lens[lv[nz], run[nz]].sum()
-        df[s] = defs[lv[nz], run[nz]].sum()
-    return tb, df
+from mdec_hard_content import curves, luts      # noqa: F401  (the one copy of the curve code)
 
 
 if __name__ == "__main__":
