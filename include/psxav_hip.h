@@ -181,6 +181,63 @@ int psxhip_mdec_query_geometry(int device, int codec, int width, int height, int
 #define PSXHIP_MDEC_STATS_TOTAL (PSXHIP_MDEC_STATS_FRAME0 + PSXHIP_MDEC_TRACE_FRAMES)
 int psxhip_mdec_read_stats(psxhip_mdec_ctx_t *ctx, unsigned long long *out, int n, int reset);
 
+/* ---------------------------------------------------------------- MDEC BS frame decoder ---- */
+
+/* The way back: bitstream -> quantised levels -> NV21 pixels, and the per-frame sum of squared errors of two sets of frames -- a
+ * preview of what a player shows, a quality figure per frame, and a verify step that keeps up with the encoder.  The reference has
+ * no decoder; the syntax is its encoder's (psxavenc/mdec.c:441-510), the reconstruction arithmetic is this library's own, in
+ * integers ("psxhip MDEC reconstruct v1").  Arbitrary bytes are safe to decode: every read is bounded by the
+ * frame's byte count, bits past the end read as 0, and a frame that does not parse gets a status, not a fault. */
+enum {
+	PSXHIP_DEC_OK = 0,
+	PSXHIP_DEC_EHEADER = -1,      /* fewer than 8 bytes, or bytes 2..3 are not 00 38 */
+	PSXHIP_DEC_EVERSION = -2,     /* version neither 2 nor 3 */
+	PSXHIP_DEC_EPREMATURE = -3,   /* v2: the end code where a block's DC belongs */
+	PSXHIP_DEC_EDC = -4,          /* v3: no DC size class starts with these bits */
+	PSXHIP_DEC_EAC = -5,          /* no AC code starts with these bits */
+	PSXHIP_DEC_EOVERRUN = -6,     /* a run leads past coefficient 63 */
+	PSXHIP_DEC_EENDCODE = -7,     /* the blocks are not followed by the end code (0x1FF for v2, 0x3FF for v3) */
+	PSXHIP_DEC_ETRUNCATED = -8    /* the end code lies past the frame's last byte */
+};
+
+typedef struct {
+	int32_t status;              /* PSXHIP_DEC_*: the first error in stream order */
+	int32_t quant_scale;         /* the header's field (0 when the magic is wrong) */
+	int32_t version;             /* 2 or 3 (the header's field when it is neither; 0 when the magic is wrong) */
+	int32_t bits_consumed;       /* payload bits up to and including the end code; 0 unless status is PSXHIP_DEC_OK */
+} psxhip_mdec_decoded_t;
+
+typedef struct psxhip_mdec_decoder psxhip_mdec_decoder_t;
+
+/* width/height: multiples of 16, at most 1024 each.  dc_wrap: non-zero = v3 DC values wrap to 10 bits (streams of codec v3dc). */
+int psxhip_mdec_decoder_create(psxhip_mdec_decoder_t **dec, int device, int width, int height, int dc_wrap);
+void psxhip_mdec_decoder_destroy(psxhip_mdec_decoder_t *dec);
+
+/* Decode n_frames bitstreams (frame i: d_bs_sizes[i] bytes at d_bs + i*bs_stride; d_bs_sizes NULL = uniform_size bytes each; a
+ * size above bs_stride counts as bs_stride) -- rows as psxhip_mdec_encode_frames_device writes them, bytes_used or the whole
+ * budget as the size.  d_bs and bs_stride must be 4-byte aligned.  Results:
+ *   d_decoded[i]  always
+ *   d_levels      (may be NULL) frame i's (width/16)*(height/16)*6 blocks of 64 int16 levels in zig-zag order, blocks in stream
+ *                 order (macroblocks column-major; Cr, Cb, Y0..Y3), at d_levels + i*blocks*64
+ *   d_frames      (may be NULL) the reconstructed NV21 frame at d_frames + i*frame_stride, the layout the encoder reads; 4-byte
+ *                 aligned.  With d_levels NULL the levels pass through a workspace the context owns (grown on demand).
+ * A frame whose status is not PSXHIP_DEC_OK leaves its levels unspecified and its pixels untouched; nothing outside the frame's own
+ * rows is written.  Asynchronous on `stream`, nothing is read back; calls on one context must be stream-ordered. */
+int psxhip_mdec_decode_frames_device(psxhip_mdec_decoder_t *dec, const uint8_t *d_bs, size_t bs_stride,
+                                     const int32_t *d_bs_sizes, int uniform_size, int n_frames, int16_t *d_levels,
+                                     uint8_t *d_frames, size_t frame_stride, psxhip_mdec_decoded_t *d_decoded, void *stream);
+/* Same, host buffers (levels and frames back to back, either may be NULL): H2D, kernels, D2H, synchronise. */
+int psxhip_mdec_decode_frames_host(psxhip_mdec_decoder_t *dec, const uint8_t *bs, size_t bs_stride, const int32_t *bs_sizes,
+                                   int uniform_size, int n_frames, int16_t *levels, uint8_t *frames,
+                                   psxhip_mdec_decoded_t *decoded);
+/* d_sse[i][0..2] = sum of squared differences of frame i of d_a and of d_b over the Y, Cb and Cr samples: exact integers,
+ * independent of the order of summation.  PSNR is the caller's arithmetic: 10 log10(255^2 * samples / sse).  Pointers and
+ * frame_stride 4-byte aligned; asynchronous on `stream`. */
+int psxhip_mdec_sse_device(int device, const uint8_t *d_a, const uint8_t *d_b, size_t frame_stride, int width, int height,
+                           int n_frames, uint64_t *d_sse, void *stream);
+/* revision of the decoder's kernels (profiles are keyed by it) */
+const char *psxhip_mdec_decode_kernel_rev(void);
+
 /* ---------------------------------------------------------------- SPU / XA ADPCM ----------- */
 
 /* carried state of one channel: the last two DECODED samples (libpsxav/adpcm.c:135-136).  The

@@ -7,3 +7,5 @@ by tests and bench.py: device memory and streams come from PyTorch, everything e
 from ._lib import LIB_PATH, PsxHipError, lib  # noqa: F401
 
 BS_CODEC_V2, BS_CODEC_V3, BS_CODEC_V3DC = 0, 1, 2   # bs_codec_t, psxavenc/args.h:61-65
+
+from .decode import MdecDecoder, psnr  # noqa: E402,F401
