@@ -256,11 +256,8 @@ def xa_assemble_device(d_units, n_sectors, settings, first_lba=0, d_eof=None):
 def pick_chunking(total_units, rows=5, n_cu=None):
     """(chunk_units, warmup_units) for speculate-and-verify: few verify passes vs enough chunks to fill the GPU; large jobs get
     the chunk length at which every wavefront slot (8 per SIMD) holds exactly one wavefront of `rows` chunks (same rule as
-    psxhip_audio_api.cpp; tools/gpu_adpcm_sweep.py, tools/gpu_xacd_chunk_sweep.sh).  rows: chains per wavefront, 5 for XA
+    psxhip_audio_api.cpp; tools/gpu_adpcm_sweep.py, NOTEBOOK section 4).  rows: chains per wavefront, 5 for XA
     (4 filters), 4 for SPU (5 filters)."""
-    import os
-    if os.environ.get("PSXHIP_ADPCM_CHUNK"):          # experiments only (tools/gpu_xacd_chunk_sweep.sh)
-        return int(os.environ["PSXHIP_ADPCM_CHUNK"]), int(os.environ.get("PSXHIP_ADPCM_WARM", "128"))
     if n_cu is None:
         n_cu = 256
         try:

@@ -584,7 +584,7 @@ __global__ __launch_bounds__(64, VERIFY ? 4 : 8) void adpcm_chunks_kernel(const 
                 prev2 = job.chain_states[c].prev2;
             } else {
                 warm = min(job.warmup_units, first + lead);   // may reach back before the chain (negative unit index)
-                // Where the warm-up starts from: silence, or (experiments, PSXHIP_ADPCM_SEED=1) the two RAW samples in front of it.
+                // Where the warm-up starts from: silence, or (job.seed_raw, a kept negative) the two RAW samples in front of it.
                 // The carried state is the last two DECODED samples (adpcm.c:135-136); a decoded sample differs from the raw one by
                 // less than a quantiser step, so the raw history is within a step of the truth where silence is a whole amplitude
                 // away.  It does not help (VERDICT r04 #3b, oracle/cpu_bench converge, profiles/r05_adpcm_convergence.txt): two
@@ -1193,8 +1193,7 @@ extern "C" int psxhip_adpcm_session_create(psxhip_adpcm_session_t** out, int dev
     job.warmup_units = warmup_units;
     job.filter_count = filter_count;
     job.range = bits == 4 ? 12 : 8;
-    job.seed_raw = 0;
-    if (const char* e = getenv("PSXHIP_ADPCM_SEED")) job.seed_raw = atoi(e) != 0;      // experiments: 1 = warm-ups start from the raw history (a kept negative)
+    job.seed_raw = 0;      // warm-ups start from silence (1 = from the raw history: a kept negative, see the kernel)
     job.chain_states = s->d_cstates.as<psxhip_adpcm_state_t>();
     job.lead_units = s->d_lead.as<int32_t>();
     job.start_known = s->d_known.as<uint8_t>();
@@ -1259,7 +1258,7 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
         // back: pass i + 1 looks at pass i's word when it starts and returns at once if nothing changed, so the host reads the
         // words once per batch -- no synchronise + launch round trip (40-50 us) per pass.  The words travel back through a
         // page-locked buffer of the session (a run is synchronous).
-        constexpr int kBatchMax = 64;          // (the flags' room; batches grow 3, 6, 12, 16, 16 ... unless PSXHIP_ADPCM_VERIFY_BATCH says otherwise)
+        constexpr int kBatchMax = 64;          // (the flags' room; batches grow 3, 6, 12, 16, 16 ...)
         int*& h_flags = s->h_flags;      // owned by the session (a buffer per calling thread leaked one per worker thread of the multi-device calls)
         if (!h_flags && hipHostMalloc((void**)&h_flags, kBatchMax * sizeof(int), hipHostMallocDefault) != hipSuccess) {
             h_flags = nullptr;
@@ -1284,10 +1283,9 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
             if (any_change) *any_change = 1;
         }
         // first batch: most material is done after "one pass that repairs + one that finds nothing"
-        // (experiments, PSXHIP_ADPCM_VERIFY_BATCH=n: every batch n passes -- with n = 48 a short stream's whole verify phase is ONE
-        //  batch, no host round trip in it: what the round trips cost, tools/gpu_r06_verify_batch.sh)
-        static const int forced_batch = [] { const char* e = getenv("PSXHIP_ADPCM_VERIFY_BATCH"); const int v = e ? atoi(e) : 0; return v > 64 ? 64 : v; }();
-        int batch = forced_batch > 0 ? forced_batch : 3;
+        // (measured, NOTEBOOK round 6: with every batch 48 passes a short stream's whole verify phase is ONE batch, no host round trip
+        //  in it -- the round trips cost nothing measurable)
+        int batch = 3;
         for (bool done = false; !done;) {
             if (max_passes > 0 && passes + batch > max_passes) batch = max_passes - passes;
             if (batch < 1) {
@@ -1309,7 +1307,7 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
                 if (h_flags[i]) { if (any_change) *any_change = 1; }
                 else done = true;              // it changed nothing: the fixpoint; the passes behind it returned at once
             }
-            batch = forced_batch > 0 ? forced_batch : (batch * 2 < 16 ? batch * 2 : 16);
+            batch = batch * 2 < 16 ? batch * 2 : 16;
         }
         if (timed) {
             TRY(hipEventRecord(s->ev[2], st));

@@ -543,15 +543,6 @@ struct psxhip_scaler {
     int n_cus;
 };
 
-#define HIP_TRY(expr, code)                                                                   \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return (code);                                                                    \
-        }                                                                                     \
-    } while (0)
-
 extern "C" void psxhip_scaler_destroy(psxhip_scaler_t* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);

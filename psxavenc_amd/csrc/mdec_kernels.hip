@@ -51,14 +51,6 @@ constexpr int kTileStride = 72;   // int16 per block in the transpose tile: 6 bl
 constexpr int kZStride = 64;      // int16 per block in the coefficient tile: column-pass lane t stores its 8 outputs at bytes 16 t
 constexpr int kPilotMax = 4;      // scales evaluated per pilot round
 constexpr int kMaxTiles = 16;     // image tiles of 2048 dwords: budgets up to 128 KiB
-// profiling builds (-DPSX_EXP_STOP_AFTER=n, WRONG BYTES, every frame ends after its first pass): a macroblock's work stops after
-// 1 = ticket + pixel fetch, 2 = + DCT, 3 = + coefficient read and list build.  PMC differences between them and the product build
-// are where the instruction inventory in DESIGN.md comes from (tools/gpu_pmc_quick.sh, tools/build_variant.sh).
-#ifdef PSX_EXP_STOP_AFTER
-constexpr int kStopAfter = PSX_EXP_STOP_AFTER;
-#else
-constexpr int kStopAfter = 0;
-#endif
 constexpr uint32_t kNoMb = 0xFFFFu;   // pass order entry without a macroblock (the last round of tickets may be partial)
 constexpr uint32_t kRetryEmpty = 0xFFFFFFFFu, kRetryAbandoned = 0xFFFFFFFEu;
 // Frame tickets and the retry queue's state share one 64-bit word of the ticket buffer, in a cache line of its own: fresh-frame
@@ -144,7 +136,7 @@ __device__ __forceinline__ BatchPtr batch_table() {
 // the arguments the frame loop reads now and then -- the ticket plan, the trust mode, the queue's patience -- are loaded at kernel
 // entry and kept, one scalar register each for the whole kernel, in a kernel that spills a hundred of them: mdec-k3.7's four new
 // ones pushed the frame pointer of the macroblock loop out of its scalar pair (two v_readfirstlane and a v_readlane more per
-// macroblock: +1.5 % vector instructions, found with the instruction counters of tools/gpu_r05_session_p.sh).
+// macroblock: +1.5 % vector instructions, found with the instruction counters, NOTEBOOK round 5).
 #define PSX_JOB_INT(member) (((FirstPtr)((const char __attribute__((address_space(4)))*)batch_table() + offsetof(FrameJob, member)))[0])
 // the retry queue's slots, the address made where it is used (one thread, rarely): as a loop invariant the 64-bit address sat in
 // two vector registers -- or a scratch slot -- for the whole kernel
@@ -1098,12 +1090,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 const int luma_items = (H >> 3) * gpr, total_items = luma_items + (H >> 4) * gpr;
                 const int r = lane & 7, cl = lane >> 3;
                 auto item_addr = [&](int item, bool& chroma, int& R, int& c, bool& ok) -> const uint8_t* {
-#ifdef PSX_EXP_DC_REVERSE      // experiment: walk the frame bottom to top, luma and chroma interleaved, so that what the main pass reads first was read last
-                    if (item < total_items) {
-                        const int t = total_items - 1 - item, k = t / (3 * gpr), r = t - k * 3 * gpr;
-                        item = r < 2 * gpr ? 2 * k * gpr + r : luma_items + k * gpr + (r - 2 * gpr);
-                    }
-#endif
                     chroma = item >= luma_items;
                     const int it2 = chroma ? item - luma_items : item;
                     R = it2 / gpr;
@@ -1646,7 +1632,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         // follows from the spread of the sample's macroblocks (finite-population form).  Stopping costs a quarter
                         // pass and is right when the verdict is; carrying on costs a whole pass when it is wrong: stop when the
                         // projection is wrong-sided by more than ck_margin / 1000 standard errors (1.0; 0.8 until mdec-k3.7's closing session -- swept over nine workloads
-                        // with tools/gpu_ckmargin_sweep.py: content whose answer flips between neighbouring scales gains 14 %
+                        // (NOTEBOOK section 3, Mapping): content whose answer flips between neighbouring scales gains 14 %
                         // over a fixed 5 % margin, stable content is unaffected).
                         int margin = (limit_bits - fixed_bits) / 50;
                         if (emit_scale && records_ok && done > 1 && done < nmb) {
@@ -1694,8 +1680,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     uint32_t b_lo, b_hi;
                     mb_bytes(ts, b_lo, b_hi);
                     fetch_behind(nxt_o.x & 0x7FFFFFFFu, nxt_o.y & 0xFFFFu, b_lo, b_hi);
-                    if (kStopAfter == 1) { asm volatile("" :: "v"(b_lo), "v"(b_hi)); }
-                    else if (valid) dct_mb(ts, b_lo, b_hi);
+                    if (valid) dct_mb(ts, b_lo, b_hi);
                 }
                 cur_t = nxt_t;
                 cur_o = nxt_o;
@@ -1703,7 +1688,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 nxt_o = order_at(nxt_t);
                 if (!valid) continue;
                 mb_done++;
-                if (kStopAfter == 1 || kStopAfter == 2) continue;
 
                 int ci[6];       // this lane's coefficient (scan position = lane) of each block; lane 0 (the DC slot) holds 0
 #pragma unroll
@@ -1787,7 +1771,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             dense = count > 128;
                         }
                     }
-                    if (kStopAfter == 3) { asm volatile("" :: "s"(count)); wave_sync(); return; }
                     if (dense) {
                         float cff[6];
 #pragma unroll
@@ -2123,7 +2106,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 }
                 }
             }
-            if (kStopAfter && tid == 0) L.scalars[S_DONE] = 1;
             group_sync(4);
         }
         mark(3);   // passes
@@ -2538,33 +2520,8 @@ extern "C" int psxhip_mdec_pass_order(int width, int height, int large, uint32_t
     // order: a round's twelve macroblocks read 192-byte pieces of pixel rows, memory is fetched in 128-byte granules, and with
     // EVERY round scattered the half-used granules at a round's ends were gone from L2 before the neighbouring round came
     // (fetch 141 MB per 1000 frames of 320x240 against 115 MB of pixels; 123 MB with three quarters of the rounds in raster order).  Scattering all rounds in runs
-    // of 3 or 5 neighbours instead (tools/gpu_pass_run_sweep.sh) saves as much but changes what the checkpoint samples -- three
+    // of 3 or 5 neighbours instead (NOTEBOOK round 4) saves as much but changes what the checkpoint samples -- three
     // adjacent macroblock rows are no sample of a picture -- and moved noisy content by -12 .. +14 %.
-    // (experiment, PSXHIP_MDEC_SAMPLE_CLUSTER=c: the quarter's sample as clusters of c neighbouring macroblocks spread over the frame
-    //  instead of whole rounds of `waves` neighbours -- 18 clusters of 4 where the default has 6 of 12 at 320x240)
-    int cluster = 0;
-    if (const char* e = getenv("PSXHIP_MDEC_SAMPLE_CLUSTER")) cluster = atoi(e);
-    if (cluster > 0 && cluster < waves && trips >= 8) {
-        const int K = (nmb + cluster - 1) / cluster, Q = (trips >> 2) * waves;
-        int stepk = (K * 382 + 500) / 1000;
-        for (;; stepk++) { int x = stepk, y = K; while (y) { const int t = x % y; x = y; y = t; } if (x == 1) break; }
-        char* usedmb = (char*)calloc((size_t)nmb, 1);
-        if (!usedmb) return -1;
-        int t = 0;
-        for (int j = 0; j < K && t < Q; j++) {
-            const int k = (int)(((long long)j * stepk) % K);
-            for (int m = k * cluster; m < (k + 1) * cluster && m < nmb && t < Q; m++) {
-                if (t < cap) out[t] = (uint32_t)(m % nx) | (uint32_t)(m / nx) << 8;
-                usedmb[m] = 1;
-                t++;
-            }
-        }
-        for (int m = 0; m < nmb; m++)
-            if (!usedmb[m]) { if (t < cap) out[t] = (uint32_t)(m % nx) | (uint32_t)(m / nx) << 8; t++; }
-        for (; t < n; t++) if (t < cap) out[t] = kNoMb;
-        free(usedmb);
-        return n;
-    }
     int* seq = (int*)malloc((size_t)trips * sizeof(int));      // ticket round -> raster round (a permutation)
     char* used = (char*)calloc((size_t)trips, 1);
     if (!seq || !used) { free(seq); free(used); return -1; }

@@ -77,7 +77,7 @@ struct SplitJob {
     int hint;                        // the answer of this context's previous one-frame call (0: none): where the speculative streams are built
     unsigned* done_flag;             // page-locked host word the last group stores done_seq into once the frame's row and result are written (one-frame calls), or NULL
     unsigned done_seq;
-    unsigned long long* dbg;         // diagnostics (PSXHIP_MDEC_SPLIT_DBG): [group][8] wall-clock stamps at the phase boundaries, or NULL
+    unsigned long long* dbg;         // diagnostics: [group][8] wall-clock stamps at the phase boundaries, or NULL (what the host passes)
     unsigned long long patience;     // ticks a rendezvous waits (kSplitPatience; PSXHIP_MDEC_SPLIT_PATIENCE)
     int wh_frame, wh_seg, wh_residue;   // PSXHIP_MDEC_SPLIT_WITHHOLD (tests): segment wh_seg of frame wh_frame never arrives (wh_seg < 0: off)
 };
@@ -689,7 +689,7 @@ extern "C" hipError_t psxhip_mdec_split_launch(const psxhip_mdec_split_t* a) {
     job.ws = (unsigned char*)a->d_ws; job.ws_stride = a->geo.ws_stride;
     job.ws_slots = a->geo.ws_slots; job.ws_dcq = a->geo.ws_dcq; job.ws_img = a->geo.ws_img; job.ws_done = a->geo.ws_done; job.img_words = a->geo.img_words;
     job.lost = a->d_lost;
-    job.dbg = a->d_dbg;
+    job.dbg = nullptr;
     job.done_flag = a->d_done_flag; job.done_seq = a->done_seq; job.hint = a->hint;
     job.patience = a->patience ? a->patience : kSplitPatience;
     job.wh_frame = a->wh_frame; job.wh_seg = a->wh_seg < a->geo.segs ? a->wh_seg : -1; job.wh_residue = a->wh_residue;

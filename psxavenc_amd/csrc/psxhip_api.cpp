@@ -36,15 +36,6 @@ struct SplitGate {
 SplitGate g_split_gate[64];
 bool g_tables_ready[64] = {false};
 
-#define HIP_TRY(expr, code)                                                                   \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return (code);                                                                    \
-        }                                                                                     \
-    } while (0)
-
 int ensure_device(int device) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
@@ -103,11 +94,7 @@ struct psxhip_mdec_ctx {
     bool lane_pending[2];           // lane_done[l] has been recorded and no caller stream has been ordered behind it yet
     int retry_patience;
     int trust_mode;                 // experiments (PSXHIP_MDEC_TRUST): 1 = foreign hints always trusted, 2 = never
-    bool spare_groups;              // PSXHIP_MDEC_SPARE (experiments, measured and not used)
-    int max_run;                    // longest run of consecutive frames a frame ticket may be (4; PSXHIP_MDEC_RUN: experiments)
     unsigned long long* d_stats;    // diagnostics (PSXHIP_MDEC_STATS=1)
-    unsigned prio_pattern;
-    int ck_margin;
     uint32_t* d_order;              // the order a pass's tickets visit the macroblocks (psxhip_mdec_pass_order)
     uint32_t* d_order_large;        // ... for the 16-wavefront shape, when small batches may use it (see encode_frames_device)
     int n_cu;
@@ -140,14 +127,9 @@ struct psxhip_mdec_ctx {
     unsigned char* d_split_ws;        // [kLanes][split_max] per-frame workspaces, all zero between launches
     size_t split_ws_stride;
     int split_max;                    // launches of at most this many frames take the split kernel (0: never)
-    unsigned long long* d_split_dbg;  // diagnostics (PSXHIP_MDEC_SPLIT_DBG=1): phase stamps of the last split launch
-    int split_dbg_groups;
     unsigned long long split_patience;   // tests (PSXHIP_MDEC_SPLIT_PATIENCE): ticks a rendezvous waits (0: the kernel's default)
     int wh_frame, wh_seg, wh_launches, wh_residue;   // tests (PSXHIP_MDEC_SPLIT_WITHHOLD): see mdec_split.inc; wh_launches = 0: off
     long long split_launches;         // split launches of this context so far
-    // diagnostics (PSXHIP_PERCALL_TRACE=1): where a one-frame call's host time goes, printed when the context is destroyed
-    bool call_trace;
-    double call_ns[6];                // copy in, stage-in launch, encode launch, wait, copy out, calls
 };
 
 namespace {
@@ -171,16 +153,6 @@ int mdec_geometry(int width, int height, int max_frame_size, size_t lds_cu, int*
             if ((shape ? 1 : 2) * psxhip_mdec_lds_bytes(nmb, t + 2, sw, shape) <= lds_cu) {
                 lg = shape;
                 ow = t + 2;
-            }
-        }
-    }
-    if (const char* e = getenv("PSXHIP_MDEC_LARGE")) {           // experiments: force the large shape
-        if (atoi(e) && !lg) {
-            lg = 1;
-            ow = 0;
-            for (int i = 0; i < 4 && !ow; i++) {
-                const int t = tiles[i] < image ? tiles[i] : image;
-                if ((image + t - 1) / t <= 16 && psxhip_mdec_lds_bytes(nmb, t + 2, sw, 1) <= lds_cu) ow = t + 2;
             }
         }
     }
@@ -271,21 +243,10 @@ extern "C" int psxhip_mdec_create(psxhip_mdec_ctx_t** out, int device, int codec
     // opt the kernels into the whole LDS once (contexts with different geometries share the kernel attribute)
     HIP_TRY(psxhip_mdec_set_max_lds(codec, lds_cu), PSXHIP_EDEVICE);
     c->groups_max = prop.multiProcessorCount * (c->large ? 1 : 2);
-    if (const char* e = getenv("PSXHIP_MDEC_GRID")) { const int g = atoi(e); if (g > 0 && g < c->groups_max) c->groups_max = g; }   // experiments
     // the kernel's leave word packs four 16-bit sums, to each of which a group adds at most 63 (kTrustCap): the grid stays below
     // 65535 / 63 groups so that none carries into its neighbour (1040; MI355X: 512)
     if (c->groups_max > 1040) c->groups_max = 1040;
-    c->spare_groups = getenv("PSXHIP_MDEC_SPARE") != nullptr;      // experiments; read once
-    c->prio_pattern = 0x2EE01u;      // younger group raised 6 steps in 8, older 1 (re-swept on mdec-k2.23: tools/gpu_prio_sweep.py)
-    if (const char* e = getenv("PSXHIP_MDEC_PRIO")) c->prio_pattern = (unsigned)strtoul(e, nullptr, 0);
-    if (const char* e = getenv("PSXHIP_MDEC_CKMARGIN")) c->ck_margin = atoi(e);      // experiments (tools/gpu_ckmargin_sweep.py)
-    // Runs of consecutive frames per ticket are built and measured, and NOT the default: what made
-    // scene-structured content fast is the trust policy (pilot when foreign hints fail); on top of it runs of 2 / 4 changed mixed
-    // content by -2 .. +5 % and cost uniform content 10 % with two launch lanes (groups that finish while their launch's other
-    // groups have yet to start may not wait for handed-on frames).  PSXHIP_MDEC_RUN=2 / 4 turns them on.
-    c->max_run = 1;
     if (const char* e = getenv("PSXHIP_MDEC_TRUST")) c->trust_mode = atoi(e);
-    if (const char* e = getenv("PSXHIP_MDEC_RUN")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) c->max_run = v; }      // experiments: 1 = single-frame tickets
 
     c->lanes = 1;
     HIP_TRY(hipMalloc((void**)&c->d_ticket, kLanes * 128 * sizeof(unsigned int)), PSXHIP_ENOMEM);
@@ -301,7 +262,6 @@ extern "C" int psxhip_mdec_create(psxhip_mdec_ctx_t** out, int device, int codec
     //  would otherwise take two of the device's few hardware queues -- streams are dealt onto them round-robin -- and with three
     //  contexts alive two callers' streams shared one queue: their launches ran one after the other)
     c->n_cu = prop.multiProcessorCount;
-    c->call_trace = getenv("PSXHIP_PERCALL_TRACE") != nullptr;
     c->call_no_flush = getenv("PSXHIP_NO_HDP_FLUSH") != nullptr;
     {
         // one frame across many workgroups, for launches of at most split_max frames (PSXHIP_MDEC_SPLIT_MAX: experiments, 0 = off).
@@ -331,7 +291,6 @@ extern "C" int psxhip_mdec_create(psxhip_mdec_ctx_t** out, int device, int codec
             const size_t bytes = (size_t)(kLanes + 1) * c->split_max * g.ws_stride;
             HIP_TRY(hipMalloc((void**)&c->d_split_ws, bytes), PSXHIP_ENOMEM);
             HIP_TRY(hipMemset(c->d_split_ws, 0, bytes), PSXHIP_EDEVICE);
-            if (getenv("PSXHIP_MDEC_SPLIT_DBG")) HIP_TRY(hipMalloc((void**)&c->d_split_dbg, (size_t)c->split_max * c->n_cu * 8 * sizeof(unsigned long long)), PSXHIP_ENOMEM);
         } else {
             c->split_max = 0;
         }
@@ -339,7 +298,7 @@ extern "C" int psxhip_mdec_create(psxhip_mdec_ctx_t** out, int device, int codec
     // A batch of at most one frame per CU gains nothing from the two-group shape (its point is two frames per CU): such
     // launches use the 16-wavefront shape, which finishes a lone frame sooner -- the drop-in one-frame-per-call pattern most
     // of all.  Needs that shape's pass order too, and its (larger) LDS working set to fit.
-    const bool both = !c->large && psxhip_mdec_lds_bytes(c->nmb, c->out_words, c->stg_words, 1) <= lds_cu && !getenv("PSXHIP_MDEC_NO_SMALL_BATCH_SHAPE");
+    const bool both = !c->large && psxhip_mdec_lds_bytes(c->nmb, c->out_words, c->stg_words, 1) <= lds_cu;
     for (int shape = c->large; shape <= (both ? 1 : c->large); shape++) {
         const int n = psxhip_mdec_pass_table(width, height, shape, nullptr, 0);
         const size_t tab_bytes = ((size_t)n + 1) * 2 * sizeof(uint32_t);          // n tickets + the all-zero entry behind them
@@ -392,11 +351,7 @@ extern "C" void psxhip_mdec_destroy(psxhip_mdec_ctx_t* c) {
     if (c->d_order) (void)hipFree(c->d_order);
     if (c->d_order_large) (void)hipFree(c->d_order_large);
     if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->call_trace && c->call_ns[5] > 0)
-        fprintf(stderr, "per-call trace (%.0f calls, us per call): copy in %.2f, stage-in launch %.2f, encode launch %.2f, wait %.2f, copy out %.2f\n", c->call_ns[5],
-                c->call_ns[0] / c->call_ns[5] * 1e-3, c->call_ns[1] / c->call_ns[5] * 1e-3, c->call_ns[2] / c->call_ns[5] * 1e-3, c->call_ns[3] / c->call_ns[5] * 1e-3, c->call_ns[4] / c->call_ns[5] * 1e-3);
     if (c->d_split_ws) (void)hipFree(c->d_split_ws);
-    if (c->d_split_dbg) (void)hipFree(c->d_split_dbg);
     psxhip_mdec_free_staging(c);
     if (c->h_call) (void)hipHostFree(c->h_call);
     if (c->d_call_frame) (void)hipFree(c->d_call_frame);
@@ -432,8 +387,6 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
             sp.hint = d_done_flag ? c->call_hint : 0;
             if (flagged) *flagged = d_done_flag != nullptr;
             sp.d_lost = c->d_ticket + 128 * lane + 3;
-            sp.d_dbg = c->d_split_dbg;
-            c->split_dbg_groups = sp.geo.segs * n_frames;
             sp.stream = stream;
             sp.patience = c->split_patience;
             sp.wh_seg = -1;
@@ -442,11 +395,6 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
                 sp.wh_frame = c->wh_frame;
                 sp.wh_seg = w == INT_MIN ? segs / 2 : (w < 0 ? (segs + w >= 0 ? segs + w : 0) : (w < segs ? w : segs - 1));
                 sp.wh_residue = c->wh_residue;
-            }
-            static const bool no_gate = getenv("PSXHIP_NO_SPLIT_GATE") != nullptr;      // experiments only: what happens without the gate (tests/test_gpu_split_threads.py)
-            if (no_gate) {
-                HIP_TRY(psxhip_mdec_split_launch(&sp), PSXHIP_EDEVICE);
-                return PSXHIP_OK;
             }
             SplitGate& gate = g_split_gate[c->device & 63];
             std::unique_lock<std::mutex> lk(gate.mu);
@@ -487,9 +435,12 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
     a.out_tile = c->out_words - 2;
     a.max_frame_size = c->max_frame_size;
     a.stg_words = c->stg_words;
-    // frame tickets: runs of consecutive frames (a group encodes neighbours in time one after the other: the hint that is worth
-    // trusting), long runs first (psxhip_mdec_ticket_plan)
-    psxhip_mdec_ticket_plan(n_frames, c->groups_max, c->max_run, &a.t4, &a.t2, &a.n_tickets);
+    // frame tickets: one frame each.  Runs of consecutive frames per ticket (psxhip_mdec_ticket_plan's max_run 2 / 4) are built and
+    // measured, and NOT used (NOTEBOOK round 5): what made scene-structured content fast is the trust policy
+    // (pilot when foreign hints fail); on top of it runs of 2 / 4 changed mixed content by -2 .. +5 % and cost uniform content
+    // 10 % with two launch lanes (groups that finish while their launch's other groups have yet to start may not wait for
+    // handed-on frames).
+    psxhip_mdec_ticket_plan(n_frames, c->groups_max, 1, &a.t4, &a.t2, &a.n_tickets);
     a.grid = a.n_tickets < c->groups_max ? a.n_tickets : c->groups_max;
     a.large = c->large || small_batch;
     a.stream = stream;
@@ -499,18 +450,13 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
     // frame, and a group holds FEW: from about eight frames per group on the fresh-frame tickets level the groups by themselves,
     // and a frame restarted on another XCD is read from HBM again (10 000 x 640x480: -1 % time, +8 % traffic with the queue)
     const bool queue = c->d_retry && n_frames > a.grid && n_frames <= 8 * a.grid && n_frames < c->retry_cap;
-    // (experiments, PSXHIP_MDEC_SPARE: a launch of at most one run per group has CU slots to spare when runs left some empty -- 1000 frames:
-    //  500 runs on 512 slots -- and the kernel lets groups start without a ticket, to take handed-on frames only.  Measured: they
-    //  never get any, because a group that finds not every group of its launch started may not wait and gives its place up at
-    //  once; not used.)
-    if (queue && a.n_tickets < c->groups_max && n_frames > a.n_tickets && c->spare_groups) a.grid = c->groups_max;
     a.d_retry = queue ? c->d_retry + (size_t)lane * c->retry_cap : nullptr;
     a.retry_cap = queue ? c->retry_cap : 0;
     a.retry_patience = c->retry_patience;
     a.d_order = small_batch ? c->d_order_large : c->d_order;
     a.d_stats = c->d_stats;
-    a.prio_pattern = c->prio_pattern;
-    a.ck_margin = c->ck_margin;
+    a.prio_pattern = 0x2EE01u;      // younger group raised 6 steps in 8, older 1 (re-swept on mdec-k2.23: NOTEBOOK section 3, Mapping)
+    a.ck_margin = 0;                // the kernel's default margin
     a.trust_mode = c->trust_mode;
     HIP_TRY(psxhip_mdec_launch(&a), PSXHIP_EDEVICE);
     return PSXHIP_OK;
@@ -827,9 +773,6 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
         if (c->h_call) {
             if (!c->stream) HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking), PSXHIP_EDEVICE);
             const size_t fpad = c->call_out_off;
-            struct timespec ts[6];
-            auto tick = [&](int k) { if (c->call_trace) clock_gettime(CLOCK_MONOTONIC, &ts[k]); };
-            tick(0);
             if (c->call_bar) {
                 // write-combined stores through the BAR, then the HDP flush that puts them in the device's memory: a register write,
                 // posted like the stores in front of it and like the doorbell behind it -- the device takes them in that order
@@ -839,13 +782,10 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
                     *c->hdp_flush = 1u;
                     __builtin_ia32_sfence();
                 }
-                tick(1);
             } else {
                 memcpy(c->h_call, frames, fsz);
-                tick(1);
                 HIP_TRY(psxhip_mdec_stage_in_launch(c->d_call, c->d_call_frame, fpad, c->stream), PSXHIP_EDEVICE);
             }
-            tick(2);
             psxhip_mdec_batch_t bd;
             bd.d_frames = c->d_call_frame; bd.n_frames = 1; bd.reserved = 0; bd.d_frame_max_sizes = nullptr;
             bd.d_out = c->d_call + c->call_out_off; bd.d_results = (psxhip_mdec_result_t*)(c->d_call + c->call_res_off);
@@ -857,7 +797,6 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
             std::unique_lock<std::mutex> gate_hold;          // (split launches of a device go one behind the other: see SplitGate)
             int rc = mdec_launch_lane(c, 0, &bd, 1, (fsz + 3) & ~(size_t)3, one, dstride, c->stream, (unsigned*)(c->d_call + c->call_res_off + 32), seq, &flagged, &gate_hold);
             if (rc) return rc;
-            tick(3);
             if (flagged) {
                 // the kernel's last group raises the flag when row and result are in this block: a look at our own memory instead of
                 // the stream's completion signal.  (A flag that does not come within 2 ms: the stream is waited for.)
@@ -878,24 +817,6 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
                 HIP_TRY(hipStreamSynchronize(c->stream), PSXHIP_EDEVICE);
             }
             if (gate_hold.owns_lock()) gate_hold.unlock();
-            tick(4);
-            if (c->d_split_dbg) {          // diagnostics: where a split launch's time goes (one line per call on stderr)
-                static int shown = 0;
-                const int g = c->split_dbg_groups;
-                std::vector<unsigned long long> t((size_t)g * 8);
-                if (g > 0 && shown++ % 100 == 50 && hipStreamSynchronize(c->stream) == hipSuccess && hipMemcpy(t.data(), c->d_split_dbg, t.size() * 8, hipMemcpyDeviceToHost) == hipSuccess) {
-                    unsigned long long t0 = ~0ull;
-                    for (int i = 0; i < g; i++) if (t[(size_t)i * 8] < t0) t0 = t[(size_t)i * 8];
-                    fprintf(stderr, "split dbg (%d groups; ticks of 10 ns since the first group's start: min / max over groups)", g);
-                    static const char* nm[8] = {"start", "dct", "counted", "met", "emitted", "left", "flag up", "last done"};
-                    for (int k = 0; k < 8; k++) {
-                        unsigned long long lo = ~0ull, hi = 0;
-                        for (int i = 0; i < g; i++) { const unsigned long long v = t[(size_t)i * 8 + k]; if (v < t0) continue; if (v - t0 < lo) lo = v - t0; if (v - t0 > hi) hi = v - t0; }
-                        fprintf(stderr, "  %s %llu/%llu", nm[k], lo == ~0ull ? 0 : lo, hi);
-                    }
-                    fprintf(stderr, "\n");
-                }
-            }
             memcpy(results, c->h_call + c->call_res_off, sizeof(psxhip_mdec_result_t));
             if (flagged && results[0].quant_scale == PSXHIP_MDEC_QS_RELEASED) {
                 // a frame whose groups the watchdog released (another process holding the CUs for 0.2 s): the frame kernel encodes it
@@ -907,11 +828,6 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
                 memcpy(results, c->h_call + c->call_res_off, sizeof(psxhip_mdec_result_t));
             }
             memcpy(out, c->h_call + c->call_out_off, (size_t)max_size);
-            if (c->call_trace) {
-                tick(5);
-                for (int k = 0; k < 5; k++) c->call_ns[k] += (double)(ts[k + 1].tv_sec - ts[k].tv_sec) * 1e9 + (double)(ts[k + 1].tv_nsec - ts[k].tv_nsec);
-                c->call_ns[5] += 1.0;
-            }
             c->call_hint = results[0].quant_scale < 64 ? results[0].quant_scale : 0;
             if (results[0].quant_scale >= 64) {
                 psxhip_set_error("frame %d does not fit %d bytes at any quant scale", 0, one);
@@ -922,9 +838,8 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
     }
     // chunk: most of a GPU-load of frames -- small enough that a 1000-frame call already pipelines staging, DMA and kernel
     // over three chunks (353 k frames/s against 269 k with 1024-frame chunks), large enough for launches to stay efficient
-    // (tools/gpu_chunk_sweep.py)
+    // (NOTEBOOK section 7)
     int chunk = c->groups_max * 3 / 4;
-    if (const char* e = getenv("PSXHIP_MDEC_CHUNK")) { const int v = atoi(e); if (v > 0) chunk = v; }      // experiments
     const size_t staging_cap = (size_t)96 << 20;                  // pinned bytes per staging buffer
     if ((size_t)chunk * fsz > staging_cap) chunk = (int)(staging_cap / fsz);
     if (chunk < 1) chunk = 1;

@@ -12,27 +12,13 @@ int psxhip_ensure_device(int device);
 
 namespace {
 
-#define HIP_TRY(expr, code)                                                                   \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return (code);                                                                    \
-        }                                                                                     \
-    } while (0)
-
 // streams at least this long are also split along time (psxhip_adpcm_encode_chains_chunked)
-const int kChunkedThreshold = []() {
-    if (const char* e = getenv("PSXHIP_ADPCM_CHUNK_THRESHOLD")) { const int v = atoi(e); if (v >= 64) return v; }      // experiments
-    return 4096;
-}();
+constexpr int kChunkedThreshold = 4096;
 // ... and from 512 units when the call has only a few chains: one chain of 788 blocks (config `spu`'s second of audio) encoded serially
 // by one wavefront takes 1.35 ms, cut along time 0.98 ms; 2048 blocks 3.35 ms against 0.97 (the chunked path's set-up and verify round
-// trips are ~0.75 ms whatever the length, so below ~500 units serial wins; tools/gpu_r05_session_k.sh).  Many short chains keep the
+// trips are ~0.75 ms whatever the length, so below ~500 units serial wins; NOTEBOOK section 4).  Many short chains keep the
 // serial kernel: it runs them all side by side.
 inline int chunked_threshold(int n_chains) {
-    static const bool forced = getenv("PSXHIP_ADPCM_CHUNK_THRESHOLD") != nullptr;      // experiments; read once
-    if (forced) return kChunkedThreshold;
     return n_chains <= 8 ? 512 : kChunkedThreshold;
 }
 
@@ -43,12 +29,8 @@ inline int chunked_threshold(int n_chains) {
 // slot of the GPU (8 per SIMD) holds exactly ONE wavefront of `rows` chunks: the encoder is a dependent chain per unit, so a
 // SIMD with four wavefronts runs its VALU at 84 % and one with eight at ~100 %, and a launch of 3.7 wavefronts per SIMD ends
 // when the SIMDs that drew four do (config 5, 78 M units on one GPU: 1899 instead of 4096 units per chunk, 21.3 -> 24.4 M
-// sectors/s, still two verify passes; 1266: three passes, 950: four -- tools/gpu_xacd_chunk_sweep.sh).
+// sectors/s, still two verify passes; 1266: three passes, 950: four -- NOTEBOOK section 4).
 inline void pick_chunking(long long total_units, int rows, int device, int* chunk_units, int* warmup_units) {
-    // experiments (tools/gpu_r06_chunk_sweep.sh): PSXHIP_ADPCM_CHUNK / PSXHIP_ADPCM_WARM fix both, read once
-    static const int forced_chunk = [] { const char* e = getenv("PSXHIP_ADPCM_CHUNK"); return e ? atoi(e) : 0; }();
-    static const int forced_warm = [] { const char* e = getenv("PSXHIP_ADPCM_WARM"); return e ? atoi(e) : 128; }();
-    if (forced_chunk > 0) { *chunk_units = forced_chunk; *warmup_units = forced_warm; return; }
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
     const long long per_round = 32ll * n_cu * rows;                        // chunks in flight when every slot holds a wavefront

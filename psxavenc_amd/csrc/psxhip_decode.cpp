@@ -11,15 +11,6 @@
 
 int psxhip_ensure_device(int device);
 
-#define HIP_TRY(expr, code)                                                                   \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return (code);                                                                    \
-        }                                                                                     \
-    } while (0)
-
 struct psxhip_mdec_decoder {
     int device, width, height, nblk, wrap;
     int16_t* d_ws = nullptr;          // levels of a call that wants pixels only

@@ -60,7 +60,6 @@ typedef struct {
 	psxhip_mdec_split_geo_t geo;
 	void *d_ws;                         /* geo.ws_stride x n_frames bytes, all zero between launches (the kernel leaves it so) */
 	unsigned int *d_lost;               /* frames given up by the rendezvous watchdog */
-	unsigned long long *d_dbg;          /* diagnostics: [groups][8] phase stamps, or NULL */
 	unsigned int *d_done_flag;          /* one-frame calls: a page-locked host word (device address) that receives done_seq when row and result are written, or NULL */
 	unsigned int done_seq;
 	int hint;                           /* the answer of the context's previous one-frame call (0: none) */
@@ -168,3 +167,13 @@ void psxhip_set_error(const char *fmt, ...);
 #ifdef __cplusplus
 }
 #endif
+
+/* a failed HIP call: its text goes to psxhip_last_error() and the calling function returns `code` */
+#define HIP_TRY(expr, code)                                                                   \
+    do {                                                                                      \
+        hipError_t e__ = (expr);                                                              \
+        if (e__ != hipSuccess) {                                                              \
+            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
+            return (code);                                                                    \
+        }                                                                                     \
+    } while (0)

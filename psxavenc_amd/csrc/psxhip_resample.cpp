@@ -14,15 +14,6 @@
 
 int psxhip_ensure_device(int device);
 
-#define HIP_TRY(expr, code)                                                                   \
-    do {                                                                                      \
-        hipError_t e__ = (expr);                                                              \
-        if (e__ != hipSuccess) {                                                              \
-            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__); \
-            return (code);                                                                    \
-        }                                                                                     \
-    } while (0)
-
 namespace {
 
 constexpr int kFilterSize = 32;         // libswresample's defaults: filter_size, phase_shift (1 << 10 phases), cutoff, Kaiser beta

@@ -109,3 +109,19 @@ def test_no_gpu_means_loud_failure():
     with pytest.raises(_lib.PsxHipError) as e:
         MdecEncoder(0, 320, 240)
     assert e.value.code == _lib.PSXHIP_EDEVICE
+
+
+def test_every_environment_switch_is_listed_in_integration_md():
+    """the names in getenv("...") under psxavenc_amd/csrc/ are exactly the rows of INTEGRATION.md's switch table (section 6): a switch
+    nobody lists is a code path nobody tests"""
+    read = set()
+    csrc = os.path.join(ROOT, "psxavenc_amd", "csrc")
+    for path in sorted(glob.glob(os.path.join(csrc, "*"))):
+        if os.path.isfile(path) and not path.endswith((".o", ".checked")):
+            read |= set(re.findall(r'getenv\(\s*"([^"]+)"\s*\)', open(path, errors="replace").read()))
+    assert read, "no getenv found under %s" % csrc
+    section = open(os.path.join(ROOT, "INTEGRATION.md")).read().split("## 6. Environment switches", 1)
+    assert len(section) == 2, "INTEGRATION.md has no section '6. Environment switches'"
+    listed = re.findall(r"^\| `([A-Z][A-Z0-9_]*)` \|", section[1], re.M)
+    assert len(listed) == len(set(listed)), "a switch is listed twice"
+    assert set(listed) == read, "read but not listed: %s; listed but not read: %s" % (sorted(read - set(listed)), sorted(set(listed) - read))

@@ -1,7 +1,7 @@
 """Soak of the frame kernel's hint / pilot / trust-policy paths (mdec-k3.7): scene-structured sequences (psxavenc_amd/mixed.py: runs of
 5..30 similar frames, cuts between noise amplitudes, hand-made flat / hard-edge / escape frames) with random per-frame budgets, several
-consecutive launches per encoder context (the verdict on foreign hints travels from launch to launch), one lane and two, single-frame
-tickets and runs of 2 / 4 -- every output byte and result field against the oracle (encoded on all host cores).
+consecutive launches per encoder context (the verdict on foreign hints travels from launch to launch), one lane and two -- every
+output byte and result field against the oracle (encoded on all host cores).
 usage: gpu_soak_mixed.py [rounds [seed [frames per launch]]]"""
 import os, sys, time
 from concurrent.futures import ThreadPoolExecutor
@@ -34,7 +34,6 @@ for rnd in range(rounds):
     w, h = [(320, 240), (320, 240), (160, 112), (640, 480)][rnd % 4]
     n = N if w <= 320 else max(64, N // 4)
     launches = int(rng.integers(2, 5))
-    run = int(rng.choice([1, 1, 2, 4]))
     lanes = int(rng.integers(1, 3))
     seq = mixed.frames_host(O, w, h, int(rng.integers(1, 1 << 20)), int(rng.integers(0, 5000)), n * launches)
     lo = 8 + 2 * (((w // 16) * (h // 16) * 6 * 12 + 10 + 15) // 16)
@@ -49,9 +48,7 @@ for rnd in range(rounds):
     m = seq.shape[0] // launches
     if m < 8:
         continue
-    os.environ["PSXHIP_MDEC_RUN"] = str(run)
     enc = MdecEncoder(codec, w, h, max_frame_size=stride)
-    del os.environ["PSXHIP_MDEC_RUN"]
     if lanes > 1:
         enc.set_lanes(2)
     d_seq, d_bud = torch.from_numpy(seq).to("cuda:0"), torch.from_numpy(budgets).to("cuda:0")
@@ -71,7 +68,7 @@ for rnd in range(rounds):
     total += m * launches
     bad += 0 if ok else 1
     sc = np.unique(want_res[:m * launches, 0])
-    print("round %3d codec %d %dx%d %d x %d frames run %d lanes %d scales %d..%d (%d distinct): %s   [%d frames, %.0f s]"
-          % (rnd, codec, w, h, launches, m, run, lanes, sc.min(), sc.max(), sc.size, "ok" if ok else "MISMATCH", total, time.time() - t0), flush=True)
+    print("round %3d codec %d %dx%d %d x %d frames lanes %d scales %d..%d (%d distinct): %s   [%d frames, %.0f s]"
+          % (rnd, codec, w, h, launches, m, lanes, sc.min(), sc.max(), sc.size, "ok" if ok else "MISMATCH", total, time.time() - t0), flush=True)
 print("soak (mixed content): %d frames in %d rounds, %d mismatching rounds" % (total, rounds, bad))
 sys.exit(1 if bad else 0)
