@@ -541,7 +541,6 @@ struct ChunkJob {
     const int32_t* chunk_first;      // [n_chunks] first unit (chain-local) of each chunk
     int n_chunks, chunk_units, warmup_units;
     int filter_count, range;
-    int seed_raw;                    // speculate: the warm-up starts from the two RAW samples in front of it instead of from silence (see the kernel)
     const psxhip_adpcm_state_t* chain_states;   // start state of every chain (the truth as far as it is known)
     const int32_t* lead_units;                  // [n_chains] units available BEFORE the chain's first unit for guessing
                                                 //            its start state (0: start from chain_states as given)
@@ -584,21 +583,8 @@ __global__ __launch_bounds__(64, VERIFY ? 4 : 8) void adpcm_chunks_kernel(const 
                 prev2 = job.chain_states[c].prev2;
             } else {
                 warm = min(job.warmup_units, first + lead);   // may reach back before the chain (negative unit index)
-                // Where the warm-up starts from: silence, or (job.seed_raw, a kept negative) the two RAW samples in front of it.
-                // The carried state is the last two DECODED samples (adpcm.c:135-136); a decoded sample differs from the raw one by
-                // less than a quantiser step, so the raw history is within a step of the truth where silence is a whole amplitude
-                // away.  It does not help (VERDICT r04 #3b, oracle/cpu_bench converge, profiles/r05_adpcm_convergence.txt): two
-                // encoders on the same samples do not merge when they are CLOSE, they merge when they are EQUAL, and a difference of
-                // one unit in the last place survives the predictor's rounding for hundreds of units on tonal material whatever it
-                // started as (two tones + noise floor, 64 warm-up units: 116 units to the truth from silence, 108 from raw history;
-                // pure tone 252 / 239; noise and quiet material fall in within a unit either way).  Only the guess would change;
-                // verify makes the result the serial encode's either way.
-                const long long s0 = (long long)(first - warm) * 28;
-                if (job.seed_raw && s0 - 2 >= -(long long)lead * 28) {
-                    const int16_t* sp = job.samples + ch.sample_offset;
-                    prev1 = s0 - 1 < ch.sample_limit ? (int)sp[(s0 - 1) * ch.pitch] : 0;
-                    prev2 = s0 - 2 < ch.sample_limit ? (int)sp[(s0 - 2) * ch.pitch] : 0;
-                }
+                // The warm-up starts from silence.  Starting from the two raw samples in front of it is a kept negative: it does not
+                // converge sooner (oracle/cpu_bench converge, profiles/r05_adpcm_convergence.txt).
             }
         } else {
             // (scalars, not structs: a conditional between two loaded structs went through a stack slot -- 12 bytes of scratch per
@@ -1193,7 +1179,6 @@ extern "C" int psxhip_adpcm_session_create(psxhip_adpcm_session_t** out, int dev
     job.warmup_units = warmup_units;
     job.filter_count = filter_count;
     job.range = bits == 4 ? 12 : 8;
-    job.seed_raw = 0;      // warm-ups start from silence (1 = from the raw history: a kept negative, see the kernel)
     job.chain_states = s->d_cstates.as<psxhip_adpcm_state_t>();
     job.lead_units = s->d_lead.as<int32_t>();
     job.start_known = s->d_known.as<uint8_t>();

@@ -65,7 +65,8 @@ constexpr int kStartedWord = 96;         // groups of this launch that have star
 constexpr int kLeaveWord = 8;
 constexpr int kLeaveWrongShift = 32, kLeaveTriedShift = 48;
 constexpr unsigned kTrustCap = 63u;
-constexpr int kNoTicket = 0x7FFFFFFF;   // S_FRAME of a group that holds no fresh-frame ticket (any more): it takes frames from the retry queue
+constexpr float kCkMargin = 1000.0f;     // quarter-pass checkpoint: how far (thousandths of its standard error) a projection has to be on the wrong side
+constexpr int kNoTicket = 0x7FFFFFFF;   // S_FRAME of a group that has run out of fresh-frame tickets (end_of_frame): it takes frames from the retry queue
 constexpr int kPilotWord = 10;           // (64 bits) what the groups learned about the PILOT's guesses: wrong | tried << 32, added before the group counts itself out
 constexpr int kDistrustWord = 4;         // hint[kDistrustWord]: the launches before this one found foreign hints wrong more than one time in four (shared by the context's lanes, like the hint)
 constexpr int kQueueReservedShift = 32, kQueueHeadShift = 48;
@@ -100,7 +101,7 @@ struct FrameJob {
     size_t frame_stride;
     int width, height, nx, ny, nmb;
     int n_frames;                  // over all batches
-    int n_tickets, t4, t2;         // frame tickets of the launch: the first t4 are runs of 4 consecutive frames, the next t2 runs of 2, the rest single frames (ticket_run())
+    int n_tickets;                 // frame tickets of the launch: ticket t is frame t (= n_frames)
     int uniform_max_size;
     size_t out_stride;
     int out_words;           // LDS dwords reserved for the frame image tile (out_tile + 2)
@@ -115,9 +116,7 @@ struct FrameJob {
     unsigned int* retry;     // [retry_cap] retry queue: frame | scale to start from << 24, kRetryEmpty when vacant (NULL: frames are never handed on)
     int retry_patience;      // looks (about 3 us each) a group without work waits for a frame to be handed on
     int retry_cap;
-    unsigned prio_pattern;       // [7:0] older group, [15:8] younger group: bit (iteration & 7) = raised priority
     int trust_mode;              // 0: the trust policy (below); experiments: 1 = foreign hints always trusted (the kernels before mdec-k3.7), 2 = never
-    int ck_margin;               // quarter-pass checkpoint: how far (thousandths of its standard error) a projection has to be on the wrong side
     unsigned long long* stats;   // optional [PSXHIP_MDEC_STATS]: pass counters (diagnostics), NULL in normal runs
     uint32_t col_k[16];          // the column pass's sixteen coefficient pairs (col_coeffs()), fetched by ONE scalar load per macroblock
 };
@@ -133,7 +132,7 @@ __device__ __forceinline__ BatchPtr batch_table() {
     return p;
 }
 // An int member of the kernel argument, loaded where it is asked for (a scalar load from the argument segment): as plain members
-// the arguments the frame loop reads now and then -- the ticket plan, the trust mode, the queue's patience -- are loaded at kernel
+// the arguments the frame loop reads now and then -- the ticket count, the trust mode, the queue's patience -- are loaded at kernel
 // entry and kept, one scalar register each for the whole kernel, in a kernel that spills a hundred of them: mdec-k3.7's four new
 // ones pushed the frame pointer of the macroblock loop out of its scalar pair (two v_readfirstlane and a v_readlane more per
 // macroblock: +1.5 % vector instructions, found with the instruction counters, NOTEBOOK round 5).
@@ -149,18 +148,6 @@ __device__ __forceinline__ unsigned long long* queue_state(const FrameJob& job) 
 // the next fresh-frame ticket: the low half of the state word (what the waiting groups look at)
 __device__ __forceinline__ unsigned draw_ticket(const FrameJob& job) { return (unsigned)atomicAdd(queue_state(job), 1ull); }
 __device__ __forceinline__ unsigned long long* leave_word(const FrameJob& job) { return (unsigned long long*)&job.ticket[kLeaveWord]; }
-// Frame ticket t -> its run of consecutive frames.  Runs are what gives a frame a hint worth trusting: inside a run a group encodes
-// neighbours in time one after the other, and the answer of frame f - 1 is the best predictor of frame f there is (decoded video:
-// scenes of similar frames).  With single-frame tickets handed out in index order a group's previous frame lies a whole round of the
-// grid back -- 512 frames: another scene.  Long runs first, short ones at the end (the host sizes t4 / t2 so that every round of
-// the grid is whole, psxhip_mdec_launch): guided self-scheduling, the tail of a launch is still balanced frame by frame.
-__device__ __forceinline__ void ticket_run(const FrameJob& job, int t, int& first, int& len) {
-    const int t4 = PSX_JOB_INT(t4), t2 = PSX_JOB_INT(t2), t42 = t4 + t2;
-    if (t < t4) { first = 4 * t; len = 4; }
-    else if (t < t42) { first = 4 * t4 + 2 * (t - t4); len = 2; }
-    else { first = 4 * t4 + 2 * t2 + (t - t42); len = 1; }
-}
-
 // scalars[] slots (LDS, per workgroup).  [0, S_KEEP0) are per-frame: cleared when a frame ends; [S_KEEP0, S_COUNT) live across frames.
 enum {
     S_DC_BITS = 0,      // v3: sum of the DC code lengths
@@ -194,16 +181,16 @@ enum {
     S_PILOT_BITS0 = S_PILOT_SCALE0 + kPilotMax,   // [kPilotMax]
     S_TILE_FIRST0 = S_PILOT_BITS0 + kPilotMax,    // [kMaxTiles + 1] first macroblock whose stream starts in image tile t (see the merge)
     S_KEEP0 = S_TILE_FIRST0 + kMaxTiles + 1,
-    S_FRAME = S_KEEP0,  // the frame TICKET in hand (a ticket is a run of 1, 2 or 4 consecutive frames: ticket_run())
-    S_FIDX,             // index of the frame being encoded (inside the ticket's run, or a frame taken from the retry queue)
-    S_RUN_LEFT,         // frames of the ticket's run behind the one being encoded
+    S_FRAME = S_KEEP0,  // the frame TICKET in hand (ticket t is frame t), kNoTicket when no fresh one is left
+    S_FIDX,             // index of the frame being encoded (the ticket's frame, or a frame taken from the retry queue)
+    S_RUN_LEFT,         // always 0: a ticket is one frame.  It stays, with end_of_frame's `left > 0` arm and hand_on's term: read from LDS the compiler cannot fold it, and every form of the kernel without it spilled more in the 12-wavefront v3 shapes than tests/test_kernel_resources.py allows (NOTEBOOK, mdec-k3.8)
     S_PUSHED,           // the previous fresh frame of this group was handed on (see hand_on: whose hint the next frame starts from)
     S_QUEUE,            // drawn with the last frame's end when no fresh ticket is left: >= 0 the queue slot to take, -1 nothing will come, <= -2 wait for slot -2 - x
     S_HINT,             // the previous frame's answer in this group (0 = none): the pilot starts from it
     S_HINT_BUDGET,      // ... and its budget
     S_HINT_FRAME,       // ... and its index: the hint is the neighbour's answer when that is this frame's index - 1 (inside a run), foreign otherwise
     S_SHARED_HINT,      // answer | budget << 8 of the previous launch's last frame (by index)
-    S_NEXT_DRAW,        // thread 0's ticket for the run after this one, parked here over the passes (it is a register from the draw to the start of the next frame's passes: the atomic's round trip hides behind a frame's work, and the passes have no register to spare)
+    S_NEXT_DRAW,        // thread 0's ticket for the frame after this one, parked here over the passes (it is a register from the draw to the start of the next frame's passes: the atomic's round trip hides behind a frame's work, and the passes have no register to spare)
     S_REPILOT,          // the first pass, started from a hint, was stopped with a verdict FAR from the hint (a scene cut): the verdict.  The frame starts over from the pilot: one more turn of the frame loop for the same frame (taken back to 0 once the pilot has read it)
     S_DISTRUST,         // foreign hints are not trusted: frames without a neighbour's answer run the pilot (trust policy, below): bit 0 the launches before this one found them wrong more than one time in four, bits 8.. this group's foreign hints that failed in a row
     S_F_TRIED,          // foreign hints this group could judge (the frame's answer became known here)
@@ -815,7 +802,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
     // ends up finishing its last frame alone on a half-empty CU.  Wave slot numbers tell the two groups apart (the
     // first group on a SIMD holds the low slots); the groups take turns at raised priority, one macroblock at a time.
     const unsigned hw_slot = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) ;   // HW_REG_HW_ID[3:0] = wave slot on its SIMD
-    const unsigned prio_bits = (WAVES == kWavesSmall && hw_slot >= (unsigned)(kWavesSmall / 4)) ? (job.prio_pattern >> 8) & 0xFFu : job.prio_pattern & 0xFFu;
+    // bit (iteration & 7) = raised priority: the younger group is raised 6 steps in 8, the older 1 (re-swept on mdec-k2.23: NOTEBOOK section 3, Mapping)
+    constexpr unsigned kPrioOlder = 0x01u, kPrioYounger = 0xEEu;
+    const unsigned prio_bits = (WAVES == kWavesSmall && hw_slot >= (unsigned)(kWavesSmall / 4)) ? kPrioYounger : kPrioOlder;
     const unsigned prio_bits4 = prio_bits * 0x01010101u;      // the pattern four times over: bit (iteration & 31) is bit (iteration & 7)
     if (tid == 0) {
         L.scalars[S_HINT] = 0; L.scalars[S_HINT_BUDGET] = 0; L.scalars[S_HINT_FRAME] = -2; L.scalars[S_SHARED_HINT] = (int)pro_shared_hint;
@@ -876,9 +865,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
     // from it before the next frame's decisions, so the atomic's round trip hides behind a frame's work (adding gridDim.x -- a
     // scalar load -- on the spot made the compiler wait for the atomic right there, at every frame's end)
     unsigned next_draw = 0;
-    // draws below this are real tickets (the first gridDim.x tickets are the groups' own; a launch may have more groups than tickets --
-    // the surplus only ever takes frames from the retry queue)
-    auto fresh_draws = [&]() -> unsigned { const unsigned nt = (unsigned)PSX_JOB_INT(n_tickets); return nt > gridDim.x ? nt - gridDim.x : 0u; };     // (made where it is asked for: hand_on, rarely)
+    // draws below this are real tickets (the first gridDim.x tickets are the groups' own: the host launches at most one group per ticket)
+    auto fresh_draws = [&]() -> unsigned { return (unsigned)PSX_JOB_INT(n_tickets) - gridDim.x; };     // (made where it is asked for: hand_on, rarely)
     // a group's first frame is its own index (no waiting for an atomic every group issues at the same moment); the counter
     // hands out the frames after those
     if (tid == 0) {
@@ -890,27 +878,14 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         // phases, and still a time-interleaved sample of the batch (which is what real, slowly varying video wants).
         unsigned f0 = blockIdx.x;
         if ((f0 | 7u) < gridDim.x) f0 = (f0 & ~7u) + (((f0 & 7u) + (f0 >> 3)) & 7u);
-        const int n_tickets = PSX_JOB_INT(n_tickets);
-        L.scalars[S_FRAME] = (int)f0 < n_tickets ? (int)f0 : in_loop(kNoTicket);
-        // A group draws the ticket for its NEXT run when it enters the LAST frame of the run in hand -- one frame ahead of the
-        // need, and not before: "this group holds a further fresh frame" (what allows it to hand a frame on, hand_on) is then
-        // "frames left in the run, or the ticket in hand is a real one", and the draw that comes up blank still marks the moment
-        // the group enters its last fresh frame, which is what the retry queue's protocol counts on.
-        int first = 0, len = 1;
-        if ((int)f0 < n_tickets) ticket_run(job, (int)f0, first, len);
-        L.scalars[S_FIDX] = first;
-        L.scalars[S_RUN_LEFT] = len - 1;
-        if ((int)f0 >= n_tickets) {
-            // more groups than tickets (a launch of at most one run per group whose frames may be handed on): this group only ever
-            // takes frames from the queue; it draws its place there right away
-            if (job.retry) {
-                const unsigned long long w = atomicAdd(queue_state(job), 1ull << kQueueHeadShift);
-                const unsigned h = (unsigned)(w >> kQueueHeadShift) & kQueueMask, reserved = (unsigned)(w >> kQueueReservedShift) & kQueueMask;
-                L.scalars[S_QUEUE] = reserved > h ? (int)h : (unsigned)w >= (unsigned)n_tickets ? -1 : -2 - (int)h;
-            }
-        } else if (len == 1) {
-            next_draw = draw_ticket(job);
-        }
+        L.scalars[S_FRAME] = (int)f0;       // (a real ticket: psxhip_mdec_launch refuses a grid larger than the tickets)
+        // A group draws the ticket for its NEXT frame when it enters the frame in hand -- one frame ahead of the need, and
+        // not before: "this group holds a further fresh frame" (what allows it to hand a frame on, hand_on) is then "the
+        // ticket parked in S_NEXT_DRAW is a real one", and the draw that comes up blank still marks the moment the group
+        // enters its last fresh frame, which is what the retry queue's protocol counts on.
+        L.scalars[S_FIDX] = (int)f0;
+        L.scalars[S_RUN_LEFT] = 0;
+        next_draw = draw_ticket(job);
         if (job.retry) atomicAdd(&job.ticket[kStartedWord], 1u);      // (nobody waits for a frame to be handed on before all groups are here)
     }
     // Per-frame state (frame image tile, staging area, scalars) is cleared, and the next ticket published, while a frame's
@@ -919,10 +894,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         for (int i = tid; i < job.stg_words; i += kThreads) L.stg[i] = 0u;
         if (tid < S_KEEP0) L.scalars[tid] = 0;
         if (tid == 0) {
-            // tickets hand runs out in order, so workgroups that draw cheap frames simply draw more
+            // tickets hand frames out in order, so workgroups that draw cheap frames simply draw more
             if (parked) next_draw = (unsigned)L.scalars[S_NEXT_DRAW];
             const int left = L.scalars[S_RUN_LEFT];
-            bool entered_last;                 // the frame this group moves to is the last of its run
+            bool entered_last;                 // a fresh frame is entered: time to draw the ticket after it
             const int held = L.scalars[S_FRAME];
             if (left > 0 && held != kNoTicket) {
                 L.scalars[S_RUN_LEFT] = left - 1;
@@ -930,16 +905,14 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 entered_last = left == 1;
             } else {
                 const int n_tickets = PSX_JOB_INT(n_tickets);
-                int t = held != kNoTicket ? (int)(next_draw + gridDim.x) : in_loop(kNoTicket);    // (a group that only takes frames from the queue holds no ticket)
+                int t = held != kNoTicket ? (int)(next_draw + gridDim.x) : in_loop(kNoTicket);    // (a group that has taken a frame from the queue holds no ticket)
                 if (t >= n_tickets) t = in_loop(kNoTicket);
                 L.scalars[S_FRAME] = t;
                 entered_last = false;
                 if (t != kNoTicket) {
-                    int first, len;
-                    ticket_run(job, t, first, len);
-                    L.scalars[S_FIDX] = first;
-                    L.scalars[S_RUN_LEFT] = len - 1;
-                    entered_last = len == 1;
+                    L.scalars[S_FIDX] = t;
+                    L.scalars[S_RUN_LEFT] = 0;
+                    entered_last = true;
                 } else if (job.retry) {
                     // no fresh frame left for this group: in place of the ticket it draws its place in the retry queue (see the top of
                     // the frame loop), in the shadow of the same write-out
@@ -1089,6 +1062,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 const int gpr = (cpr + 7) >> 3;               // chunk groups per row
                 const int luma_items = (H >> 3) * gpr, total_items = luma_items + (H >> 4) * gpr;
                 const int r = lane & 7, cl = lane >> 3;
+                // (made here, ahead of the loop, the compare also serves the frame's later tests of "first row of a block"; left inside
+                //  item_sums it is hoisted to the loop's entry, which dominates nothing, and made three times -- the v3 shapes then
+                //  spill two more scalars in the pilot's macroblock loop than tests/test_kernel_resources.py allows)
+                const bool row0 = r == 0;
                 auto item_addr = [&](int item, bool& chroma, int& R, int& c, bool& ok) -> const uint8_t* {
                     chroma = item >= luma_items;
                     const int it2 = chroma ? item - luma_items : item;
@@ -1117,7 +1094,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     s1 += wave::dpp_or_zero<0x4E, 0xF, 0xF>(s1);
                     s0 += wave::dpp_or_zero<0x141, 0xF, 0xF>(s0);   // row_half_mirror: all 8 rows of the chunk
                     s1 += wave::dpp_or_zero<0x141, 0xF, 0xF>(s1);
-                    if (r == 0 && ok) {
+                    if (row0 && ok) {
                         const int mbe = chroma ? c * ny + R : c * ny + (R >> 1);
                         const int b0 = chroma ? 0 : 2 + (R & 1) * 2;
                         L.dcv[mbe * 6 + b0] = (int16_t)quant_dc(s0 - 64 * 128);
@@ -1125,10 +1102,6 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     }
                 };
                 constexpr int kDcItems = 8;      // loads in flight per lane
-                // (diagnostics build only: bit 24 of the priority word runs the byte-sum read TWICE -- same results; the difference
-                //  between the two launches is what the read costs, i.e. what a v3 frame would gain if the DC terms came for free)
-                const int dc_reps = STATS && ((job.prio_pattern >> 24) & 1u) ? 2 : 1;
-                for (int rep = 0; rep < dc_reps; rep++)
                 for (int item = wid; item < total_items; item += kDcItems * kWavesPerGroup) {
                     bool ch[kDcItems], ok[kDcItems];
                     int R[kDcItems], c[kDcItems];
@@ -1631,7 +1604,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         // How far on the wrong side is "clearly"?  The projection is a sample mean scaled up; its standard error
                         // follows from the spread of the sample's macroblocks (finite-population form).  Stopping costs a quarter
                         // pass and is right when the verdict is; carrying on costs a whole pass when it is wrong: stop when the
-                        // projection is wrong-sided by more than ck_margin / 1000 standard errors (1.0; 0.8 until mdec-k3.7's closing session -- swept over nine workloads
+                        // projection is wrong-sided by more than kCkMargin / 1000 standard errors (1.0; 0.8 until mdec-k3.7's closing session -- swept over nine workloads
                         // (NOTEBOOK section 3, Mapping): content whose answer flips between neighbouring scales gains 14 %
                         // over a fixed 5 % margin, stable content is unaffected).
                         int margin = (limit_bits - fixed_bits) / 50;
@@ -1640,7 +1613,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             float var = (float)ck_sq / n - mean * mean;
                             var = var > 0.0f ? var : 0.0f;
                             const float se = 4.0f * __builtin_sqrtf(var * n * (1.0f - n / (float)nmb)) * ((float)nmb / n);
-                            margin = (int)(se * (float)PSX_JOB_INT(ck_margin) * 0.001f);
+                            margin = (int)(se * kCkMargin * 0.001f);      // (two roundings, as when the 1000 was a kernel argument: the margin decides pass counts)
                         }
                         int g = mdec_search_checkpoint_bits(*srch, count_scale, (int)pa, emit_scale, (int)pb, limit_bits, fixed_bits, margin);
                         // A verdict FAR from where a PILOTED frame started is not taken: it is a two-point extrapolation from a quarter of
@@ -2012,14 +1985,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             }
             // outside the passes a group runs short, latency-bound phases (decisions, scans, merge): let them cut ahead of the
             // partner group's VALU stream instead of queueing behind it
-            if (WAVES == kWavesSmall) {
-                switch ((job.prio_pattern >> 16) & 3u) {
-                case 0: __builtin_amdgcn_s_setprio(0); break;
-                case 1: __builtin_amdgcn_s_setprio(1); break;
-                case 2: __builtin_amdgcn_s_setprio(2); break;
-                default: __builtin_amdgcn_s_setprio(3); break;
-                }
-            }
+            if (WAVES == kWavesSmall) __builtin_amdgcn_s_setprio(2);
             flush();
             group_sync(3);
             const int verdict = L.scalars[S_ABORT];
@@ -2560,29 +2526,9 @@ extern "C" int psxhip_mdec_pass_table(int width, int height, int large, uint32_t
     return n;
 }
 
-// Frame tickets of a launch of n_frames frames on `groups` persistent workgroups (ticket_run() in the kernel reads the result):
-// whole rounds of the grid in runs of 4 while at least four rounds are left, then whole rounds in runs of 2, and what remains --
-// less than two rounds -- as one round of runs of 2 when it is more than one frame per group, else as single frames.  Every
-// round of the grid is whole, so runs cost no balance: 1000 frames on 512 groups are 500 runs of 2 (as many frames per group as
-// single tickets give), 1250 are 512 runs of 2 and 226 single frames, 4000 are 512 runs of 4 and 976 of 2.
-// max_run: 1 = single frames only (the hand-out of the kernels before mdec-k3.7), 2 = no runs of 4.
-extern "C" void psxhip_mdec_ticket_plan(int n_frames, int groups, int max_run, int* t4, int* t2, int* n_tickets) {
-    int r = n_frames, a4 = 0, a2 = 0;
-    if (groups < 1) groups = 1;
-    if (max_run >= 4) { a4 = groups * (r / (4 * groups)); r -= 4 * a4; }
-    if (max_run >= 2) {
-        const int whole = groups * (r / (2 * groups));
-        a2 = whole;
-        r -= 2 * whole;
-        if (r > groups) { a2 += r / 2; r &= 1; }
-    }
-    *t4 = a4;
-    *t2 = a2;
-    *n_tickets = a4 + a2 + r;
-}
-
 extern "C" hipError_t psxhip_mdec_launch(const psxhip_mdec_launch_t* a) {
     const int waves_ = a->large ? kWavesLarge : kWavesSmall;
+    if (a->grid > a->n_tickets) return hipErrorInvalidValue;      // every group starts with a ticket of its own
     FrameJob job;
     memset(&job, 0, sizeof job);
     job.n_batches = a->n_batches;
@@ -2603,8 +2549,6 @@ extern "C" hipError_t psxhip_mdec_launch(const psxhip_mdec_launch_t* a) {
     job.nmb = job.nx * job.ny;
     job.n_frames = a->n_frames;
     job.n_tickets = a->n_tickets;
-    job.t4 = a->t4;
-    job.t2 = a->t2;
     job.uniform_max_size = a->uniform_max_size;
     job.out_stride = a->out_stride;
     job.out_words = a->out_words;
@@ -2617,8 +2561,6 @@ extern "C" hipError_t psxhip_mdec_launch(const psxhip_mdec_launch_t* a) {
     job.retry_cap = a->retry_cap;
     job.retry_patience = a->retry_patience;
     job.stats = a->d_stats;
-    job.prio_pattern = a->prio_pattern;
-    job.ck_margin = a->ck_margin > 0 ? a->ck_margin : 1000;
     job.trust_mode = a->trust_mode;
     { constexpr ColCoeffs ck = col_coeffs(); for (int i = 0; i < 16; i++) job.col_k[i] = ck.k[i]; }
     job.trips = (job.nmb + waves_ - 1) / waves_;

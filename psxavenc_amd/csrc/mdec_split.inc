@@ -77,7 +77,6 @@ struct SplitJob {
     int hint;                        // the answer of this context's previous one-frame call (0: none): where the speculative streams are built
     unsigned* done_flag;             // page-locked host word the last group stores done_seq into once the frame's row and result are written (one-frame calls), or NULL
     unsigned done_seq;
-    unsigned long long* dbg;         // diagnostics: [group][8] wall-clock stamps at the phase boundaries, or NULL (what the host passes)
     unsigned long long patience;     // ticks a rendezvous waits (kSplitPatience; PSXHIP_MDEC_SPLIT_PATIENCE)
     int wh_frame, wh_seg, wh_residue;   // PSXHIP_MDEC_SPLIT_WITHHOLD (tests): segment wh_seg of frame wh_frame never arrives (wh_seg < 0: off)
 };
@@ -138,8 +137,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
     const int mb0 = seg * M;
     const int nm = nmb - mb0 < M ? nmb - mb0 : M;
 
-    auto stamp = [&](int k) { if (job.dbg && tid == 0) job.dbg[(size_t)blockIdx.x * 8 + k] = wall_clock64(); };
-    stamp(0);
     // ---- LDS
     size_t o = 0;
     int* sc = (int*)(smem + o);                 o += 96 * 4;
@@ -284,7 +281,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
         }
     }
 
-    stamp(1);
     bool alive = true;
     if (CODEC != 0) {
         // ---- v3: every group needs every block's DC term (mdec.c:454-479): all of them read, then the three chains here
@@ -482,7 +478,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
         if (tid < cnt && base + 1 + tid <= 63)
             __hip_atomic_store(&rslots[seg * kSplitRound + tid], (unsigned long long)(unsigned)sc[SC_LBITS + tid] | ((unsigned long long)(unsigned)sc[SC_LNNZ + tid] << 32),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (round == 0) stamp(2);
         if (withheld) { alive = false; break; }          // (a withheld group leaves behind its round-0 sums, waiting for nobody)
         // While the sums travel: every wavefront codes its macroblock at ONE candidate scale into its own buffer -- the first wavefronts of a
         // macroblock at cbase, cbase + 1 -- at the previous call's answer (neighbouring frames of a video mostly agree), or around
@@ -528,7 +523,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
             if (lane < kSplitRound) { atomicAdd(&sc[SC_TOT + lane], tot); atomicAdd(&sc[SC_NNZ + lane], nnz); atomicAdd(&sc[SC_PRE + lane], pre); }
         }
         __syncthreads();
-        if (round == 0) stamp(3);
         alive = sc[SC_DEAD] == 0;
         {
             const bool fits = lane < cnt && base + 1 + lane <= 63 && (long long)sc[SC_TOT + lane] + 10 <= (long long)limit_bits;
@@ -573,7 +567,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
         }
     }
 
-    stamp(4);
     // ---- the frame's last segment's group completes the frame, once every group has said it is done: a word per group (a counter
     //      all groups add to is served one addition after the other at the memory side: the last of 150 arrivals waited ~1.5 us)
     split_drain();
@@ -586,7 +579,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
         if (bad) sc[SC_DEAD] = 2;
     }
     __syncthreads();
-    stamp(5);
     uint8_t* outp = job.out + (size_t)f * job.out_stride;
     uint32_t* o32 = (uint32_t*)outp;
     const bool tripped = sc[SC_DEAD] != 0;
@@ -631,7 +623,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
         __syncthreads();
         if (tid == 0) __hip_atomic_store(job.done_flag, job.done_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    stamp(6);
     // the workspace goes back to zero for the next launch: device-scope stores (the next launch's device-scope loads and ORs are
     // served at the memory side; a plain store could sit in this XCD's L2)
     // (WITHHOLD with `residue`: the withheld segment's words are left as a group that comes late leaves them)
@@ -645,7 +636,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
             if (i / 3 / M != keep) __hip_atomic_store(&dcw[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int i = tid; i < segs; i += kSplitThreads)
         if (i != keep) __hip_atomic_store(&done[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    stamp(7);
     leave(tripped ? 0x10001u : 1u);
 }
 
@@ -689,7 +679,6 @@ extern "C" hipError_t psxhip_mdec_split_launch(const psxhip_mdec_split_t* a) {
     job.ws = (unsigned char*)a->d_ws; job.ws_stride = a->geo.ws_stride;
     job.ws_slots = a->geo.ws_slots; job.ws_dcq = a->geo.ws_dcq; job.ws_img = a->geo.ws_img; job.ws_done = a->geo.ws_done; job.img_words = a->geo.img_words;
     job.lost = a->d_lost;
-    job.dbg = nullptr;
     job.done_flag = a->d_done_flag; job.done_seq = a->done_seq; job.hint = a->hint;
     job.patience = a->patience ? a->patience : kSplitPatience;
     job.wh_frame = a->wh_frame; job.wh_seg = a->wh_seg < a->geo.segs ? a->wh_seg : -1; job.wh_residue = a->wh_residue;

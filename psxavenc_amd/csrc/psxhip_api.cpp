@@ -435,13 +435,10 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
     a.out_tile = c->out_words - 2;
     a.max_frame_size = c->max_frame_size;
     a.stg_words = c->stg_words;
-    // frame tickets: one frame each.  Runs of consecutive frames per ticket (psxhip_mdec_ticket_plan's max_run 2 / 4) are built and
-    // measured, and NOT used (NOTEBOOK round 5): what made scene-structured content fast is the trust policy
-    // (pilot when foreign hints fail); on top of it runs of 2 / 4 changed mixed content by -2 .. +5 % and cost uniform content
-    // 10 % with two launch lanes (groups that finish while their launch's other groups have yet to start may not wait for
-    // handed-on frames).
-    psxhip_mdec_ticket_plan(n_frames, c->groups_max, 1, &a.t4, &a.t2, &a.n_tickets);
-    a.grid = a.n_tickets < c->groups_max ? a.n_tickets : c->groups_max;
+    // frame tickets: one frame each.  Tickets of 2 or 4 consecutive frames were built and measured, and not kept (NOTEBOOK round 5):
+    // on top of the trust policy they changed mixed content by -2 .. +5 % and cost uniform content 10 % with two launch lanes.
+    a.n_tickets = n_frames;
+    a.grid = a.n_tickets < c->groups_max ? a.n_tickets : c->groups_max;     // never more groups than tickets: every group of the kernel starts with a ticket of its own
     a.large = c->large || small_batch;
     a.stream = stream;
     a.d_ticket = c->d_ticket + 128 * lane;
@@ -455,8 +452,6 @@ static int mdec_launch_lane(psxhip_mdec_ctx* c, int lane, const psxhip_mdec_batc
     a.retry_patience = c->retry_patience;
     a.d_order = small_batch ? c->d_order_large : c->d_order;
     a.d_stats = c->d_stats;
-    a.prio_pattern = 0x2EE01u;      // younger group raised 6 steps in 8, older 1 (re-swept on mdec-k2.23: NOTEBOOK section 3, Mapping)
-    a.ck_margin = 0;                // the kernel's default margin
     a.trust_mode = c->trust_mode;
     HIP_TRY(psxhip_mdec_launch(&a), PSXHIP_EDEVICE);
     return PSXHIP_OK;

@@ -7,9 +7,9 @@
 #include "../../include/psxav_hip.h"
 
 /* bumped with every change to the MDEC kernel: bench.py keys the committed PMC summaries on it (profiles/pmc_index.json) */
-#define PSXHIP_MDEC_KERNEL_REV "mdec-k3.7"
+#define PSXHIP_MDEC_KERNEL_REV "mdec-k3.8"
 /* ... and with every change to the ADPCM kernels (round 4's kernels count as adpcm-k4.0) */
-#define PSXHIP_ADPCM_KERNEL_REV "adpcm-k5.3"
+#define PSXHIP_ADPCM_KERNEL_REV "adpcm-k5.4"
 
 #ifdef __cplusplus
 extern "C" {
@@ -21,7 +21,7 @@ typedef struct {
 	size_t frame_stride;
 	int width, height, codec;
 	int n_frames;                         /* over all batches */
-	int n_tickets, t4, t2;                /* frame tickets: runs of 4, runs of 2, single frames (psxhip_mdec_ticket_plan) */
+	int n_tickets;                        /* frame tickets: ticket t is frame t (= n_frames) */
 	int uniform_max_size;
 	size_t out_stride;
 	int out_words;      /* LDS dwords of the frame image tile: out_tile + 2 */
@@ -37,9 +37,7 @@ typedef struct {
 	int retry_cap;
 	int retry_patience;             /* looks a group without work waits for a handed-on frame before it leaves */
 	unsigned long long *d_stats;    /* optional [PSXHIP_MDEC_STATS] diagnostics */
-	unsigned prio_pattern;          /* see FrameJob */
 	int trust_mode;                 /* 0 = the trust policy; experiments: 1 = foreign hints always trusted, 2 = never */
-	int ck_margin;                  /* checkpoint margin in thousandths of the projection's standard error (0 = default) */
 	const uint32_t *d_order;        /* psxhip_mdec_pass_table() for this geometry, in device memory */
 } psxhip_mdec_launch_t;
 
@@ -80,7 +78,6 @@ hipError_t psxhip_mdec_upload_tables(void);
 hipError_t psxhip_mdec_set_max_lds(int codec, size_t bytes);
 int psxhip_mdec_pass_order(int width, int height, int large, uint32_t *out, int cap);
 int psxhip_mdec_pass_table(int width, int height, int large, uint32_t *out /* [2 * (n + 1)] */, int cap);
-void psxhip_mdec_ticket_plan(int n_frames, int groups, int max_run, int *t4, int *t2, int *n_tickets);
 hipError_t psxhip_mdec_launch(const psxhip_mdec_launch_t *a);
 hipError_t psxhip_mdec_stage_in_launch(const void *src_mapped, void *d_dst, size_t bytes, void *stream);
 hipError_t psxhip_mdec_fdct_launch(const int16_t *d_in, int16_t *d_out, int n_blocks, void *stream);

@@ -76,12 +76,12 @@ def _innermost_loop(lines, at):
 
 
 # scalar-register spills of the frame kernel: (SGPRs spilled, spill lane operations in the loops around the three matrix instructions --
-# pilot, pilot, pass loop) as they stand on mdec-k3.7.  A round-5 edit put spills INTO the macroblock loop (+1.5 % vector instructions)
+# pilot, pilot, pass loop) as they stand on mdec-k3.8.  A round-5 edit put spills INTO the macroblock loop (+1.5 % vector instructions)
 # and was found by A/B on hardware; with these ceilings it fails here, in the GPU-less container.
 SGPR_CEILINGS = {
-    (0, 16): (86, (31, 31, 8)), (0, 12): (86, (27, 27, 10)),
-    (1, 16): (133, (34, 34, 20)), (1, 12): (133, (34, 34, 17)),
-    (2, 16): (133, (34, 34, 20)), (2, 12): (133, (34, 34, 17)),
+    (0, 16): (81, (31, 31, 8)), (0, 12): (85, (27, 27, 10)),
+    (1, 16): (128, (34, 34, 18)), (1, 12): (132, (33, 33, 15)),
+    (2, 16): (128, (34, 34, 18)), (2, 12): (132, (33, 33, 15)),
 }
 
 

@@ -56,8 +56,11 @@ def main():
                 out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", kind], env=env, capture_output=True, text=True, timeout=600)
                 line = [ln for ln in out.stdout.splitlines() if ln.startswith("AB ")]
                 if not line:
-                    print(kind, os.path.basename(lib), "FAILED", out.stderr[-400:], flush=True)
-                    continue
+                    # a child that failed may have faulted the device: nothing more is started on it
+                    print(kind, os.path.basename(lib), "FAILED (exit %d), stopping" % out.returncode, out.stderr[-400:], flush=True)
+                    if json_out:
+                        json.dump(res, open(json_out, "w"), indent=1)
+                    return 1
                 d = json.loads(line[0][3:])
                 res.setdefault(kind, {}).setdefault(os.path.basename(lib), []).append(d)
                 print(kind, rnd, os.path.basename(lib), d, flush=True)
@@ -67,4 +70,4 @@ def main():
 
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-    main()
+    sys.exit(main())
