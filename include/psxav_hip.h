@@ -336,6 +336,89 @@ int psxhip_xa_encode_streams_host(int device, int format, int stereo, int freque
                                   int samples_per_stream, const int32_t *lbas, psxhip_adpcm_state_t *states,
                                   uint8_t *out, int64_t out_stride, int finalize);
 
+/* ---------------------------------------------------------------- SPU / XA ADPCM decoder --- */
+
+/* The way back: unit records (or SPU blocks, or XA sectors) -> int16 PCM, and the sums of squared errors of two sample sets per
+ * sound unit and per chain -- an audio preview, an SNR figure per stream, a verify step behind encode + assemble, a decoder for
+ * existing .xa / .vag material.  The arithmetic is "psxhip ADPCM decode v1" (DESIGN.md section 12), in integers: the reconstruction
+ * inside the reference's encoder (libpsxav/adpcm.c:120-124, carried state :135-136).  For a unit with header byte h and codes c[i]:
+ * R = 12 (4-bit) or 8 (8-bit), s = h & 15, f = h >> 4 (& 3 when filter_count is 4), (k1, k2) = filter f's taps (0, 0 for f >= 5),
+ * t = sext16((c[i] << R) & 0xFFFF) >> s, d = clamp(t + ((k1 p1 + k2 p2 + 32) >> 6), -32768, 32767), then p2 = p1, p1 = d.
+ * Any bytes decode: a filter number >= 5 and a shift > R are reported in the unit's flag byte, the formula is applied all the same. */
+#define PSXHIP_ADPCM_FLAG_BAD_FILTER 1   /* unit flag: filter number >= 5 (decoded with k1 = k2 = 0) */
+#define PSXHIP_ADPCM_FLAG_BAD_SHIFT 2    /* unit flag: shift above 12 (4-bit) / 8 (8-bit) */
+
+/* Decode n_chains chains, each serially.  The input is unit records in exactly the encoder's layout and geometry: unit u of chain c
+ * is the record unit_base[c] + u * unit_stride, PSXHIP_ADPCM_RECORD_SIZE(bits) bytes apart; a 4-bit record is an SPU block, so an
+ * SPU / VAG body decodes as it lies (byte 1, the loop flags, is ignored).  d_units must be 16-byte aligned.  The output is int16
+ * PCM written where the encoder would have read it (sample_offset, pitch, sample_limit, n_units of the same psxhip_adpcm_chain_t):
+ * chain-local samples at index >= sample_limit are decoded -- they feed the state -- but NOT stored.  d_states[c] is read and
+ * updated (values within int16 are the caller's contract; the encoder produces no others).  Optional outputs:
+ *   d_unit_flags  one byte per record index: PSXHIP_ADPCM_FLAG_*
+ *   d_tail        28 samples per chain (4-byte aligned): all of the unit that sample_limit cuts (unit sample_limit / 28 when
+ *                 sample_limit is no multiple of 28), for psxhip_adpcm_sse_device; chains without such a unit leave theirs untouched
+ * filter_count 5 (SPU) or 4 (XA); bits 4 or 8; 8 bits with filter_count 5 is PSXHIP_EINVAL.  Asynchronous on `stream`. */
+int psxhip_adpcm_decode_chains_device(int device, const uint8_t *d_units, const psxhip_adpcm_chain_t *d_chains,
+                                      const int32_t *d_unit_base, int n_chains, int filter_count, int bits,
+                                      psxhip_adpcm_state_t *d_states, int16_t *d_samples, uint8_t *d_unit_flags, int16_t *d_tail,
+                                      void *stream);
+
+/* Same result, parallel ALONG each chain (speculate and verify, like psxhip_adpcm_encode_chains_chunked): chains are cut into chunks
+ * of chunk_units units; every chunk but a chain's first guesses its start state by decoding up to warmup_units units in front of it
+ * from a zero state; all chunks are decoded at once; verify passes decode again, from the truth, every chunk whose assumed start
+ * differs from its predecessor's end, until a pass changes nothing.  The fixpoint equals the serial decode whatever the guesses were
+ * -- and the passes are needed: with filter 1 and all codes 0 the states 0, 8 and -7 are all fixed points, so a wrong guess can
+ * survive for ever.  `chains` and `unit_base` are HOST arrays; the call synchronises.  chunk_units <= 0: chosen by the library;
+ * warmup_units < 0: 64.  max_passes <= 0: no limit (the worst case is one chunk per pass).  Returns the number of verify passes
+ * (>= 1; 0 when there is nothing to decode) or a negative error.  When max_passes runs out before a pass changed nothing, the call
+ * returns PSXHIP_EINVAL ("not converged"), d_states is left as it was, and d_samples / d_unit_flags / d_tail hold a decode that is
+ * not verified: chunks behind a wrong guess may be wrong.  Call again with more passes. */
+int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t *d_units, const psxhip_adpcm_chain_t *chains,
+                                       const int32_t *unit_base, int n_chains, int filter_count, int bits,
+                                       psxhip_adpcm_state_t *d_states, int16_t *d_samples, uint8_t *d_unit_flags, int16_t *d_tail,
+                                       int chunk_units, int warmup_units, int max_passes, void *stream);
+
+/* Sums of squared errors of two int16 sample sets under one chain table: d_unit_sse (optional; needs d_unit_base) gets one sum
+ * (a - b)^2 per sound unit at its record index -- uint64, a unit can pass 2^32 -- and d_chain_sums (optional) [c][0] = sum (a - b)^2,
+ * [c][1] = sum b^2 over the chain: exact integers, independent of the order of summation.  dB are the caller's: 10 log10([1] / [0])
+ * is the SNR of a against b.  Samples at index >= sample_limit take part as the encoder sees them: b reads as 0 without touching
+ * memory; a is what the decoder computed there, which it did not store -- d_a_tail (optional) is the d_tail of the decode call, and
+ * gives a for the unit sample_limit cuts; elsewhere past the limit (and without d_a_tail) a reads as 0 too.  With d_a the decode of
+ * what was encoded from d_b, under the same chains, a unit's sum is the reference's state->mse after that unit (adpcm.c:131-132).
+ * Asynchronous on `stream`. */
+int psxhip_adpcm_sse_device(int device, const int16_t *d_a, const int16_t *d_a_tail, const int16_t *d_b,
+                            const psxhip_adpcm_chain_t *d_chains, int n_chains, uint64_t *d_unit_sse, const int32_t *d_unit_base,
+                            uint64_t *d_chain_sums, void *stream);
+
+/* The inverse of psxhip_xa_assemble_device: n_sectors sectors of 2336 (format 0) or 2352 (format 1) bytes -> unit records in encode
+ * order, sector s giving records [s * 18 * U, (s + 1) * 18 * U), U = 8 (4-bit) or 4 (8-bit).  d_sector_status (optional) gets per
+ * sector the bits below; a sector with bits set is disassembled all the same.  Pointers 4-byte aligned; asynchronous. */
+#define PSXHIP_XA_STATUS_HEADER_COPY 1   /* a sound group's header copy differs: bytes 4..7 against 0..3, or 12..15 against 8..11 */
+#define PSXHIP_XA_STATUS_SUBHEADER 2     /* the two subheaders differ */
+#define PSXHIP_XA_STATUS_CODING 4        /* the coding byte disagrees with the call's stereo / frequency / bits */
+#define PSXHIP_XA_STATUS_EDC 8           /* the EDC is non-zero and wrong (a sector with EOF set may carry the EDC of the sector
+                                            without EOF: psx_audio_xa_encode_finalize leaves it so, adpcm.c:334-340) */
+int psxhip_xa_disassemble_device(int device, const uint8_t *d_sectors, int n_sectors, int format, int stereo, int frequency,
+                                 int bits, uint8_t *d_units, int32_t *d_sector_status, void *stream);
+
+/* Host-buffer conveniences mirroring the encode ones.  SPU: stream i's n_blocks 16-byte blocks at blocks + i * in_stride (bytes) ->
+ * 28 * n_blocks samples at samples + i * out_stride (elements); states[i] is carried in and out.  Returns samples per stream or < 0. */
+int psxhip_spu_decode_streams_host(int device, const uint8_t *blocks, int n_streams, int64_t in_stride, int n_blocks,
+                                   psxhip_adpcm_state_t *states, int16_t *samples, int64_t out_stride);
+/* XA: stream i's n_sectors sectors at sectors + i * in_stride (bytes) -> samples per channel = n_sectors * (4-bit ? 4032 : 2016) /
+ * (stereo ? 2 : 1), interleaved L,R when stereo, at samples + i * out_stride (elements); states[2 * i] / states[2 * i + 1] are the
+ * left / right channel states (mono: states[i]).  sector_status (optional): [n_streams][n_sectors] PSXHIP_XA_STATUS_* bits.
+ * Returns samples per channel and stream or < 0. */
+int psxhip_xa_decode_streams_host(int device, int format, int stereo, int frequency, int bits, const uint8_t *sectors, int n_streams,
+                                  int64_t in_stride, int n_sectors, psxhip_adpcm_state_t *states, int16_t *samples, int64_t out_stride,
+                                  int32_t *sector_status);
+/* Measurement: with the calling thread's switch on, psxhip_adpcm_decode_chains_chunked puts HIP events around its speculate launch
+ * and around its verify passes; _last_timing returns the thread's last such call's two durations in milliseconds.  Off by default. */
+int psxhip_adpcm_decode_set_timing(int on);
+int psxhip_adpcm_decode_last_timing(float *speculate_ms, float *verify_ms);
+/* revision of the ADPCM decoder's kernels (profiles are keyed by it) */
+const char *psxhip_adpcm_decode_kernel_rev(void);
+
 /* The host-buffer ADPCM entry points keep their device scratch buffers per calling thread between calls (the reference
  * calls them once per 28 samples / once per sector); this releases the calling thread's. */
 void psxhip_release_scratch(void);
