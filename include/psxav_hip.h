@@ -578,6 +578,104 @@ int psxhip_str_encode_device(psxhip_str_ctx_t *ctx, const psxhip_str_settings_t 
                              int64_t pcm_samples_per_channel, uint8_t *d_out, size_t out_stream_stride, psxhip_str_plan_t *plan,
                              void *stream);
 
+/* ---------------------------------------------------------------- STR / STRCD / STRV reader -- */
+
+/* The way back for a whole stream: muxed sectors in HBM -> every frame's bitstream as one row (what psxhip_mdec_decode_frames_device
+ * reads), the XA sectors compacted in stream order (what psxhip_xa_disassemble_device reads), one record per frame saying whether it
+ * is whole, and optionally what every sector was.  The inverse of the sector schedule and of the video sector kernel; the rules are
+ * "psxhip STR demux v1" (restated in tests/str_demux_ref.py) and are defined for arbitrary bytes: every index
+ * taken from the stream is bounded before it is used, and bad input gives status bits, never a fault.
+ *
+ * Per format (6 / 7 / 9): sector size 2336 / 2352 / 2048, subheader `sub` at 0 / 0x10 / none, chunk header (mdec.c:782-820) at
+ * P = 8 / 0x18 / 0 (mdec.c:822-829).  A sector is
+ *   audio  when the format has subheaders, settings->audio_channels != 0, sub[2] & 0x04, sub[0] == audio_xa_file (or that is -1) and
+ *          (sub[1] & 0x1F) == (audio_xa_channel & 0x1F) (or that is -1);
+ *   video  when it is not audio, the format is STRV or (sub[2] & 0x04) == 0, bytes P, P+1 are 60 01 and le16(P+2) == str_video_id (or
+ *          that is -1);
+ *   other  else (the all-zero sector of an audio slot with no samples left is one).
+ * A video sector belongs to row = frame_index - first_frame (64-bit; frame_index = le32(P+8), unsigned); outside [0, max_frames) it
+ * is dropped: counted, and it touches nothing.  It is placeable when chunk_index < chunk_count (le16(P+4), le16(P+6), its own) and
+ * (chunk_index + 1) * 2016 <= bs_stride; of the placeable sectors of one (row, chunk_index) the one at the lowest stream position is
+ * placed: its 2016 payload bytes (P+0x20) go to d_bs + row * bs_stride + chunk_index * 2016.  Row bytes no placed chunk covers are
+ * left as they were.  The lead of a row is its sector with chunk_index 0 at the lowest position, or without one its sector at the
+ * lowest position; the frame's fields are the lead's. */
+enum {
+	PSXHIP_STR_FRAME_MISSING = 1,     /* no sector in the row, or chunk_count 0, or an index in [0, chunk_count) without a placed sector */
+	PSXHIP_STR_FRAME_DUPLICATE = 2,   /* two placeable sectors share a chunk_index */
+	PSXHIP_STR_FRAME_MISMATCH = 4,    /* a sector's chunk_count / bytes_used / width / height / BS-header copy differs from the lead's, or
+	                                     the lead has chunk_index 0 and its BS-header copy differs from the first 8 bytes of its payload */
+	PSXHIP_STR_FRAME_RANGE = 8,       /* a sector of the row is not placeable */
+	PSXHIP_STR_FRAME_EDC = 16,        /* a sector of the row fails the EDC rule below */
+	PSXHIP_STR_FRAME_GEOMETRY = 32    /* settings->video_width / video_height is non-zero and differs from the lead's */
+};
+/* EDC rule for video sectors, c(a..b) = the CD-ROM EDC of those sector bytes (cdrom.c:28-41).  STRV: no check.  STRCD: bad iff
+ * le32(0x818) is neither 0 nor c(0x10..0x817).  STR: good iff le32(0x818) == c(0x10..0x817) (where the reference's muxer puts it: it
+ * hands the 2336-byte buffer to psx_cdrom_calculate_checksums as if it had 2352, filefmt.c:474), or le32(0x808) == c(0..0x807) (where
+ * it lies on a disc), or both stored words are 0.  Audio sectors are not checked here (psxhip_xa_disassemble_device does that). */
+
+typedef struct {
+	uint32_t frame_index;        /* the lead's fields: le32(P+8) */
+	int32_t chunk_count;         /* le16(P+6) */
+	int32_t chunks_placed;       /* chunk indices of the row that got a placed sector */
+	uint32_t bytes_used;         /* le32(P+0xC) */
+	int32_t width, height;       /* le16(P+0x10), le16(P+0x12) */
+	int32_t first_sector;        /* the lead's position in the stream */
+	int32_t status;              /* PSXHIP_STR_FRAME_* bits; a row without a sector: PSXHIP_STR_FRAME_MISSING and all else 0 */
+} psxhip_str_frame_info_t;
+
+typedef struct {
+	int32_t n_video, n_audio, n_other;   /* sectors by kind (dropped ones included) */
+	uint32_t first_frame;        /* the first_frame in effect; 0 when the stream has no video sector */
+	int32_t n_rows;              /* 1 + the highest row a sector fell into, or 0 */
+	int32_t n_complete;          /* rows without PSXHIP_STR_FRAME_MISSING */
+	int32_t n_dropped_video;     /* video sectors with a row outside [0, max_frames) */
+	int32_t n_dropped_audio;     /* audio sectors with an ordinal >= xa_capacity */
+} psxhip_str_summary_t;
+
+/* A reader handle owns the workspace (grown on demand) and, for psxhip_str_read_host, the device buffers and the decoder context.
+ * Calls on one handle must be stream-ordered. */
+typedef struct psxhip_str_reader psxhip_str_reader_t;
+int psxhip_str_reader_create(psxhip_str_reader_t **reader, int device);
+void psxhip_str_reader_destroy(psxhip_str_reader_t *reader);
+
+/* Take n_streams streams of n_sectors sectors apart (stream i: sectors at d_sectors + i * in_stream_stride, rows at d_bs + i *
+ * bs_stream_stride, XA sectors at d_xa + i * xa_stream_stride; d_bs_sizes, d_frame_info are [n_streams][max_frames], d_sector_table
+ * [n_streams][n_sectors], d_summary [n_streams]).  Of the settings only format, str_video_id, audio_channels, audio_xa_file,
+ * audio_xa_channel, video_width and video_height are read.
+ *   first_frame    >= 0: the frame_index of row 0; -1: the smallest frame_index of the stream's video sectors (found on the device)
+ *   d_bs_sizes     [row] = chunk_count * 2016, or 0 when the row is MISSING -- so psxhip_mdec_decode_frames_device reports a frame
+ *                  that is not whole as PSXHIP_DEC_EHEADER and the two calls compose without a host decision
+ *   d_frame_info   every row in [0, max_frames) is written
+ *   d_xa           the audio sector with ordinal k (the number of audio sectors before it in its stream) is copied whole to d_xa + k *
+ *                  sector size when k < xa_capacity, else counted as dropped; may be NULL when xa_capacity is 0
+ *   d_sector_table (optional) psxhip_str_sector_t per sector: video {0, row or -1 when dropped, chunk_index, the RANGE / EDC bits this
+ *                  sector contributed}; audio {1, -1, k, bit 0 = the EOF submode bit 0x80}; other {2, -1, -1, 0}.  For a stream this
+ *                  library muxed, read with first_frame 1, it equals psxhip_str_plan_sectors' table.
+ * Pointers and strides are 4-byte aligned, bs_stride is at least 2016, n_streams at most 65535; n_sectors == 0 is valid (every row
+ * MISSING, a zero summary).  Asynchronous on `stream`; nothing is read back. */
+int psxhip_str_demux_device(psxhip_str_reader_t *reader, const psxhip_str_settings_t *settings, int n_streams, const uint8_t *d_sectors,
+                            size_t in_stream_stride, int n_sectors, int64_t first_frame, int max_frames, uint8_t *d_bs, size_t bs_stride,
+                            size_t bs_stream_stride, int32_t *d_bs_sizes, psxhip_str_frame_info_t *d_frame_info, uint8_t *d_xa,
+                            int xa_capacity, size_t xa_stream_stride, psxhip_str_sector_t *d_sector_table,
+                            psxhip_str_summary_t *d_summary, void *stream);
+
+/* The whole reader for one stream in host memory: H2D, demux, one read-back of the summary (the only synchronisation before the end),
+ * psxhip_mdec_decode_frames_device over the max_frames rows with the demuxed sizes (dc_wrap from video_codec, the picture size from
+ * the settings), psxhip_xa_disassemble_device and the chunked ADPCM decode over the compacted XA sectors (stereo / frequency / bits
+ * from the settings), D2H.  Rows are as wide as the largest frame the settings' frame rate and CD speed allow (mdec.c:768-775).
+ *   frames            (optional) [max_frames] NV21 pictures back to back; a frame that does not decode leaves its picture as it was
+ *   frame_info, decoded   [max_frames]
+ *   pcm               (optional) room for pcm_capacity int16 (interleaved L,R when stereo); whole sectors are decoded as far as they fit,
+ *                     the others count as dropped in the summary (all of them when pcm is NULL)
+ *   xa_sector_status  (optional) PSXHIP_XA_STATUS_* per decoded XA sector
+ * Returns the samples per channel written to pcm, or a value below 0. */
+int psxhip_str_read_host(psxhip_str_reader_t *reader, const psxhip_str_settings_t *settings, const uint8_t *sectors, int n_sectors,
+                         int64_t first_frame, int max_frames, uint8_t *frames, psxhip_str_frame_info_t *frame_info,
+                         psxhip_mdec_decoded_t *decoded, int16_t *pcm, int64_t pcm_capacity, int32_t *xa_sector_status,
+                         psxhip_str_summary_t *summary);
+/* revision of the reader's kernels (profiles are keyed by it) */
+const char *psxhip_str_demux_kernel_rev(void);
+
 /* ---------------------------------------------------------------- SPU / VAG / SPUI / VAGI files ---- */
 
 /* The reference's encode_file_spu / encode_file_spui (psxavenc/filefmt.c:212-389, .vag header :95-162) for PCM that is

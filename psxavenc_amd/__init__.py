@@ -12,3 +12,5 @@ from .decode import MdecDecoder, psnr  # noqa: E402,F401
 from . import adpcm_decode  # noqa: E402,F401  (adpcm_decode.kernel_rev(): the revision of the ADPCM decoder's kernels)
 from .adpcm_decode import (adpcm_sse, decode_chains_chunked, decode_chains_device, snr_db, spu_decode_streams,  # noqa: E402,F401
                            xa_decode_streams, xa_disassemble)
+from . import strdemux  # noqa: E402,F401  (strdemux.kernel_rev(): the revision of the STR reader's kernels)
+from .strdemux import StrReader  # noqa: E402,F401
