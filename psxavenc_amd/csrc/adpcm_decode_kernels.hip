@@ -22,6 +22,8 @@
 #include <vector>
 
 #include "adpcm_decode_core.h"
+#include "device_buffer.h"
+#include "host_layout.h"
 #include "psxhip_internal.h"
 #include "xa_edc.h"
 
@@ -482,8 +484,6 @@ void launch_decode(const DecodeJob& job, int bits, hipStream_t st) {
 
 }  // namespace
 
-int psxhip_ensure_device(int device);
-
 // measurement (psxhip_adpcm_decode_set_timing): the calling thread's switch and its last chunked call's two durations
 static thread_local bool g_timing = false;
 static thread_local float g_spec_ms = 0.f, g_verify_ms = 0.f;
@@ -577,32 +577,34 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
         return PSXHIP_EINVAL;
     }
     constexpr int kBatchMax = 16;
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o_chains = 0, o_base = o_chains + up(sizeof(psxhip_adpcm_chain_t) * n_chains), o_cc = o_base + up(4 * (size_t)n_chains);
-    const size_t o_cf = o_cc + up(4 * n_chunks), o_cp = o_cf + up(4 * n_chunks), o_last = o_cp + up(4 * n_chunks);
-    const size_t o_used = o_last + up(4 * (size_t)n_chains);
-    const size_t o_end = o_used + up(8 * n_chunks), o_flags = o_end + up(8 * n_chunks), bytes = o_flags + up(sizeof(int) * kBatchMax);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc((void**)&d, bytes), PSXHIP_ENOMEM);
+    BumpOffsets o;
+    const size_t o_chains = o.take(sizeof(psxhip_adpcm_chain_t) * n_chains), o_base = o.take(4 * (size_t)n_chains), o_cc = o.take(4 * n_chunks);
+    const size_t o_cf = o.take(4 * n_chunks), o_cp = o.take(4 * n_chunks), o_last = o.take(4 * (size_t)n_chains);
+    const size_t o_used = o.take(8 * n_chunks), o_end = o.take(8 * n_chunks), o_flags = o.take(sizeof(int) * kBatchMax);
+    DeviceBuffer ws;
+    const int rc_ws = ws.reserve(o.end);
+    if (rc_ws) return rc_ws;
+    uint8_t* const d = ws.as<uint8_t>();
     hipStream_t st = (hipStream_t)stream;
+    // declared after the workspace: on every way out the stream has come to rest before the workspace goes, and the timing events go too
+    struct AtExit {
+        hipStream_t st;
+        bool at_rest;
+        hipEvent_t ev[3];
+        ~AtExit() {
+            if (!at_rest) (void)hipStreamSynchronize(st);
+            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        }
+    } at_exit{st, false, {nullptr, nullptr, nullptr}};
+    hipEvent_t* const ev = at_exit.ev;
     int passes = 0, result = PSXHIP_OK;
     int h_flags[kBatchMax];
-#define TRY(expr)                                                                                              \
-    do {                                                                                                       \
-        hipError_t e__ = (expr);                                                                               \
-        if (e__ != hipSuccess) {                                                                               \
-            psxhip_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e__), __FILE__, __LINE__);      \
-            (void)hipStreamSynchronize(st);                                                                    \
-            (void)hipFree(d);                                                                                  \
-            return PSXHIP_EDEVICE;                                                                             \
-        }                                                                                                      \
-    } while (0)
-    TRY(hipMemcpyAsync(d + o_chains, chains, sizeof(psxhip_adpcm_chain_t) * n_chains, hipMemcpyHostToDevice, st));
-    TRY(hipMemcpyAsync(d + o_base, unit_base, 4 * (size_t)n_chains, hipMemcpyHostToDevice, st));
-    TRY(hipMemcpyAsync(d + o_cc, chunk_chain.data(), 4 * n_chunks, hipMemcpyHostToDevice, st));
-    TRY(hipMemcpyAsync(d + o_cf, chunk_first.data(), 4 * n_chunks, hipMemcpyHostToDevice, st));
-    TRY(hipMemcpyAsync(d + o_cp, chunk_pred.data(), 4 * n_chunks, hipMemcpyHostToDevice, st));
-    TRY(hipMemcpyAsync(d + o_last, last_chunk.data(), 4 * (size_t)n_chains, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d + o_chains, chains, sizeof(psxhip_adpcm_chain_t) * n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + o_base, unit_base, 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + o_cc, chunk_chain.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + o_cf, chunk_first.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + o_cp, chunk_pred.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + o_last, last_chunk.data(), 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     DecodeJob job;
     memset(&job, 0, sizeof job);
     job.units = d_units; job.chains = (const psxhip_adpcm_chain_t*)(d + o_chains); job.unit_base = (const int32_t*)(d + o_base);
@@ -613,14 +615,13 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
     job.chunk_units = chunk_units; job.warmup_units = warmup_units;
     job.start_used = (unsigned long long*)(d + o_used); job.chunk_end = (unsigned long long*)(d + o_end);
     int* d_flags = (int*)(d + o_flags);
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     const bool timed = g_timing;
     if (timed)
-        for (int i = 0; i < 3; i++) TRY(hipEventCreate(&ev[i]));
-    if (timed) TRY(hipEventRecord(ev[0], st));
+        for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]), PSXHIP_EDEVICE);
+    if (timed) HIP_TRY(hipEventRecord(ev[0], st), PSXHIP_EDEVICE);
     launch_decode<false>(job, bits, st);
-    TRY(hipGetLastError());
-    if (timed) TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
+    if (timed) HIP_TRY(hipEventRecord(ev[1], st), PSXHIP_EDEVICE);
     // verify passes in batches, back to back; a pass looks at its predecessor's word and returns at once when that changed nothing
     // (the encoder's scheme, psxhip_adpcm_session_run)
     int batch = 3;
@@ -631,15 +632,15 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
             result = PSXHIP_EINVAL;
             break;
         }
-        TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * kBatchMax, st));
+        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * kBatchMax, st), PSXHIP_EDEVICE);
         for (int i = 0; i < batch; i++) {
             job.changed = d_flags + i;
             job.changed_before = i ? d_flags + i - 1 : nullptr;
             launch_decode<true>(job, bits, st);
         }
-        TRY(hipGetLastError());
-        TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, st));
-        TRY(hipStreamSynchronize(st));
+        HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
         for (int i = 0; i < batch && !done; i++) {
             passes++;
             if (!h_flags[i]) done = true;
@@ -649,18 +650,16 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
     if (result == PSXHIP_OK) {
         hipLaunchKernelGGL(adpcm_decode_final_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, st,
                            (const int32_t*)(d + o_last), (const unsigned long long*)(d + o_end), n_chains, d_states);
-        TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
     }
     if (timed) {
-        TRY(hipEventRecord(ev[2], st));
-        TRY(hipEventSynchronize(ev[2]));
-        TRY(hipEventElapsedTime(&g_spec_ms, ev[0], ev[1]));
-        TRY(hipEventElapsedTime(&g_verify_ms, ev[1], ev[2]));
-        for (int i = 0; i < 3; i++) (void)hipEventDestroy(ev[i]);
+        HIP_TRY(hipEventRecord(ev[2], st), PSXHIP_EDEVICE);
+        HIP_TRY(hipEventSynchronize(ev[2]), PSXHIP_EDEVICE);
+        HIP_TRY(hipEventElapsedTime(&g_spec_ms, ev[0], ev[1]), PSXHIP_EDEVICE);
+        HIP_TRY(hipEventElapsedTime(&g_verify_ms, ev[1], ev[2]), PSXHIP_EDEVICE);
     }
-    TRY(hipStreamSynchronize(st));
-#undef TRY
-    (void)hipFree(d);
+    HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
+    at_exit.at_rest = true;
     return result == PSXHIP_OK ? passes : result;
 }
 

@@ -915,8 +915,6 @@ __global__ __launch_bounds__(256) void str_video_sector_kernel(const StrVideoJob
 
 }  // namespace
 
-int psxhip_ensure_device(int device);
-
 extern "C" int psxhip_adpcm_encode_chains_device(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains,
                                                  const int32_t* d_unit_base, int n_chains, int filter_count, int bits,
                                                  psxhip_adpcm_state_t* d_states, uint8_t* d_units, void* stream) {

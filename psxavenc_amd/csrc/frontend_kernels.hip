@@ -32,9 +32,8 @@
 #include <type_traits>
 #include <vector>
 
+#include "device_buffer.h"
 #include "psxhip_internal.h"
-
-int psxhip_ensure_device(int device);
 
 namespace {
 
@@ -763,18 +762,12 @@ extern "C" int psxhip_scaler_convert_host(psxhip_scaler_t* s, const uint8_t* src
     if (n_frames == 0) return PSXHIP_OK;
     HIP_TRY(hipSetDevice(s->device), PSXHIP_EDEVICE);
     const size_t fsz = (size_t)s->dw * s->dh * 3 / 2;
-    uint8_t *d_src = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_src, s->src_bytes * (size_t)n_frames), PSXHIP_ENOMEM);
-    if (hipMalloc((void**)&d_out, fsz * (size_t)n_frames) != hipSuccess) { (void)hipFree(d_src); return PSXHIP_ENOMEM; }
-    hipError_t e = hipMemcpy(d_src, src, s->src_bytes * (size_t)n_frames, hipMemcpyHostToDevice);
-    int rc = PSXHIP_OK;
-    if (e == hipSuccess) rc = psxhip_scaler_convert_device(s, d_src, s->src_bytes, n_frames, d_out, fsz, nullptr);
-    if (e == hipSuccess && rc == PSXHIP_OK) e = hipMemcpy(frames, d_out, fsz * (size_t)n_frames, hipMemcpyDeviceToHost);
-    (void)hipFree(d_src);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) {
-        psxhip_set_error("psxhip_scaler_convert_host: %s", hipGetErrorString(e));
-        return PSXHIP_EDEVICE;
-    }
-    return rc;
+    DeviceBuffer d_src, d_out;
+    int rc;
+    if ((rc = d_src.reserve(s->src_bytes * (size_t)n_frames)) || (rc = d_out.reserve(fsz * (size_t)n_frames))) return rc;
+    HIP_TRY(hipMemcpy(d_src.p, src, s->src_bytes * (size_t)n_frames, hipMemcpyHostToDevice), PSXHIP_EDEVICE);
+    rc = psxhip_scaler_convert_device(s, d_src.as<uint8_t>(), s->src_bytes, n_frames, d_out.as<uint8_t>(), fsz, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(frames, d_out.p, fsz * (size_t)n_frames, hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
+    return PSXHIP_OK;
 }

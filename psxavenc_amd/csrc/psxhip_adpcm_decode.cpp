@@ -6,18 +6,14 @@
 
 #include <vector>
 
+#include "device_buffer.h"
+#include "host_layout.h"
 #include "psxhip_internal.h"
-
-int psxhip_ensure_device(int device);
 
 namespace {
 
-struct Dev {
-    void* p = nullptr;
-    ~Dev() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 4); }
-    template <typename T> T* as() { return (T*)p; }
-};
+// a call's temporaries (never an empty allocation)
+int alloc(DeviceBuffer& b, size_t n) { return b.reserve(n ? n : 4); }
 
 // decode `chains` (host arrays) from d_units into d_samples: serial per chain, or cut along time when the chains are long
 int decode_chains(int device, const uint8_t* d_units, const std::vector<psxhip_adpcm_chain_t>& chains, const std::vector<int32_t>& base,
@@ -29,13 +25,13 @@ int decode_chains(int device, const uint8_t* d_units, const std::vector<psxhip_a
                                                           d_samples, nullptr, nullptr, 0, -1, 0, st);
         return rc < 0 ? rc : PSXHIP_OK;
     }
-    Dev d_c, d_b;
-    HIP_TRY(d_c.alloc(chains.size() * sizeof(chains[0])), PSXHIP_ENOMEM);
-    HIP_TRY(d_b.alloc(base.size() * sizeof(int32_t)), PSXHIP_ENOMEM);
+    DeviceBuffer d_c, d_b;
+    int rc;
+    if ((rc = alloc(d_c, chains.size() * sizeof(chains[0]))) || (rc = alloc(d_b, base.size() * sizeof(int32_t)))) return rc;
     HIP_TRY(hipMemcpyAsync(d_c.p, chains.data(), chains.size() * sizeof(chains[0]), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_b.p, base.data(), base.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    const int rc = psxhip_adpcm_decode_chains_device(device, d_units, d_c.as<psxhip_adpcm_chain_t>(), d_b.as<int32_t>(), n, filter_count, bits,
-                                                     d_states, d_samples, nullptr, nullptr, st);
+    rc = psxhip_adpcm_decode_chains_device(device, d_units, d_c.as<psxhip_adpcm_chain_t>(), d_b.as<int32_t>(), n, filter_count, bits, d_states,
+                                           d_samples, nullptr, nullptr, st);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);      // the tables are freed on return
     return PSXHIP_OK;
@@ -64,22 +60,16 @@ extern "C" int psxhip_spu_decode_streams_host(int device, const uint8_t* blocks,
     HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
     std::vector<psxhip_adpcm_chain_t> chains((size_t)n_streams);
     std::vector<int32_t> base((size_t)n_streams);
-    for (int i = 0; i < n_streams; i++) {
-        chains[i].sample_offset = (int64_t)i * per;
-        chains[i].pitch = 1;
-        chains[i].sample_limit = per;
-        chains[i].n_units = n_blocks;
-        chains[i].unit_stride = 1;
-        base[i] = i * n_blocks;
-    }
-    Dev d_u, d_st, d_s;
-    HIP_TRY(d_u.alloc(in_bytes * n_streams), PSXHIP_ENOMEM);
-    HIP_TRY(d_st.alloc(sizeof(psxhip_adpcm_state_t) * n_streams), PSXHIP_ENOMEM);
-    HIP_TRY(d_s.alloc(sizeof(int16_t) * (size_t)per * n_streams), PSXHIP_ENOMEM);
+    fill_planar_chains(chains.data(), base.data(), n_streams, per, 1, per, n_blocks);
+    DeviceBuffer d_u, d_st, d_s;
+    int rc;
+    if ((rc = alloc(d_u, in_bytes * n_streams)) || (rc = alloc(d_st, sizeof(psxhip_adpcm_state_t) * n_streams)) ||
+        (rc = alloc(d_s, sizeof(int16_t) * (size_t)per * n_streams)))
+        return rc;
     hipStream_t st = nullptr;
     HIP_TRY(hipMemcpy2DAsync(d_u.p, in_bytes, blocks, (size_t)in_stride, in_bytes, (size_t)n_streams, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_st.p, states, sizeof(psxhip_adpcm_state_t) * n_streams, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    const int rc = decode_chains(device, d_u.as<uint8_t>(), chains, base, 5, 4, d_st.as<psxhip_adpcm_state_t>(), d_s.as<int16_t>(), st);
+    rc = decode_chains(device, d_u.as<uint8_t>(), chains, base, 5, 4, d_st.as<psxhip_adpcm_state_t>(), d_s.as<int16_t>(), st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(samples, (size_t)out_stride * sizeof(int16_t), d_s.p, (size_t)per * sizeof(int16_t), (size_t)per * sizeof(int16_t),
                              (size_t)n_streams, hipMemcpyDeviceToHost, st), PSXHIP_EDEVICE);
@@ -97,12 +87,10 @@ extern "C" int psxhip_xa_decode_streams_host(int device, int format, int stereo,
         psxhip_set_error("xa_decode_streams_host: bad argument");
         return PSXHIP_EINVAL;
     }
-    const int ch = stereo ? 2 : 1;
-    const int upg = bits == 4 ? 8 : 4;
-    const int ssz = format == 0 ? 2336 : 2352;
-    const int units_per_stream = n_sectors * 18 * upg, units_per_chain = units_per_stream / ch;
-    const int per_channel = units_per_chain * 28;
-    const size_t per = (size_t)per_channel * ch, in_bytes = (size_t)n_sectors * ssz;
+    const XaLayout xa = xa_layout(format, stereo, bits);
+    const int ch = xa.channels, units_per_stream = n_sectors * xa.units_per_sector;
+    const int per_channel = units_per_stream / ch * 28;
+    const size_t per = (size_t)per_channel * ch, in_bytes = (size_t)n_sectors * xa.sector_bytes;
     if (n_streams == 1) { in_stride = (int64_t)in_bytes; out_stride = (int64_t)per; }
     if (n_streams > 0 && (in_stride < (int64_t)in_bytes || out_stride < (int64_t)per)) {
         psxhip_set_error("xa_decode_streams_host: in_stride %lld < %zu bytes or out_stride %lld < %zu samples per stream",
@@ -115,29 +103,20 @@ extern "C" int psxhip_xa_decode_streams_host(int device, int format, int stereo,
     HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
     std::vector<psxhip_adpcm_chain_t> chains((size_t)n_streams * ch);
     std::vector<int32_t> base((size_t)n_streams * ch);
-    for (int i = 0; i < n_streams; i++)
-        for (int c = 0; c < ch; c++) {
-            psxhip_adpcm_chain_t& d = chains[(size_t)i * ch + c];
-            d.sample_offset = (int64_t)i * (int64_t)per + c;
-            d.pitch = ch;
-            d.sample_limit = per_channel;
-            d.n_units = units_per_chain;
-            d.unit_stride = ch;
-            base[(size_t)i * ch + c] = i * units_per_stream + c;
-        }
+    fill_interleaved_chains(chains.data(), base.data(), n_streams, ch, (int64_t)per, per_channel, units_per_stream);
     const size_t total_sectors = (size_t)n_streams * n_sectors;
-    Dev d_in, d_u, d_st, d_s, d_status;
-    HIP_TRY(d_in.alloc(in_bytes * n_streams), PSXHIP_ENOMEM);
-    HIP_TRY(d_u.alloc((size_t)n_streams * units_per_stream * PSXHIP_ADPCM_RECORD_SIZE(bits)), PSXHIP_ENOMEM);
-    HIP_TRY(d_st.alloc(sizeof(psxhip_adpcm_state_t) * chains.size()), PSXHIP_ENOMEM);
-    HIP_TRY(d_s.alloc(sizeof(int16_t) * per * n_streams), PSXHIP_ENOMEM);
-    HIP_TRY(d_status.alloc(sizeof(int32_t) * total_sectors), PSXHIP_ENOMEM);
+    DeviceBuffer d_in, d_u, d_st, d_s, d_status;
+    int rc;
+    if ((rc = alloc(d_in, in_bytes * n_streams)) || (rc = alloc(d_u, (size_t)n_streams * units_per_stream * xa.record_bytes)) ||
+        (rc = alloc(d_st, sizeof(psxhip_adpcm_state_t) * chains.size())) || (rc = alloc(d_s, sizeof(int16_t) * per * n_streams)) ||
+        (rc = alloc(d_status, sizeof(int32_t) * total_sectors)))
+        return rc;
     hipStream_t st = nullptr;
     HIP_TRY(hipMemcpy2DAsync(d_in.p, in_bytes, sectors, (size_t)in_stride, in_bytes, (size_t)n_streams, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_st.p, states, sizeof(psxhip_adpcm_state_t) * chains.size(), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     // the streams' sectors lie back to back: one launch takes them all apart (a stream's records are a whole number of sectors')
-    int rc = psxhip_xa_disassemble_device(device, d_in.as<uint8_t>(), (int)total_sectors, format, stereo, frequency, bits, d_u.as<uint8_t>(),
-                                          d_status.as<int32_t>(), st);
+    rc = psxhip_xa_disassemble_device(device, d_in.as<uint8_t>(), (int)total_sectors, format, stereo, frequency, bits, d_u.as<uint8_t>(),
+                                      d_status.as<int32_t>(), st);
     if (rc) return rc;
     rc = decode_chains(device, d_u.as<uint8_t>(), chains, base, 4, bits, d_st.as<psxhip_adpcm_state_t>(), d_s.as<int16_t>(), st);
     if (rc) return rc;

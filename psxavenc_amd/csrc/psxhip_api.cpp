@@ -14,6 +14,7 @@
 #include <thread>
 #include <vector>
 
+#include "device_buffer.h"
 #include "psxhip_internal.h"
 
 namespace {
@@ -38,10 +39,7 @@ bool g_tables_ready[64] = {false};
 
 int ensure_device(int device) {
     int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-        psxhip_set_error("no HIP device visible (libpsxav_hip has no CPU fallback)");
-        return PSXHIP_EDEVICE;
-    }
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return psxhip_no_device();
     if (device < 0 || device >= n || device >= 64) {
         psxhip_set_error("device %d out of range (%d visible)", device, n);
         return PSXHIP_EINVAL;
@@ -970,19 +968,12 @@ extern "C" int psxhip_mdec_fdct_host(int device, const int16_t* blocks, int n_bl
     int rc = ensure_device(device);
     if (rc) return rc;
     if (n_blocks == 0) return PSXHIP_OK;
-    int16_t *d_in = nullptr, *d_out = nullptr;
     const size_t bytes = (size_t)n_blocks * 64 * sizeof(int16_t);
-    HIP_TRY(hipMalloc((void**)&d_in, bytes), PSXHIP_ENOMEM);
-    if (hipMalloc((void**)&d_out, bytes) != hipSuccess) { (void)hipFree(d_in); return PSXHIP_ENOMEM; }
-    hipError_t e = hipMemcpy(d_in, blocks, bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = psxhip_mdec_fdct_launch(d_in, d_out, n_blocks, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(coefs, d_out, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) {
-        psxhip_set_error("psxhip_mdec_fdct_host: %s", hipGetErrorString(e));
-        return PSXHIP_EDEVICE;
-    }
+    DeviceBuffer d_in, d_out;
+    if ((rc = d_in.reserve(bytes)) || (rc = d_out.reserve(bytes))) return rc;
+    HIP_TRY(hipMemcpy(d_in.p, blocks, bytes, hipMemcpyHostToDevice), PSXHIP_EDEVICE);
+    HIP_TRY(psxhip_mdec_fdct_launch(d_in.as<int16_t>(), d_out.as<int16_t>(), n_blocks, nullptr), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpy(coefs, d_out.p, bytes, hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
     return PSXHIP_OK;
 }
 

@@ -6,9 +6,8 @@
 #include <cstring>
 #include <vector>
 
+#include "host_layout.h"
 #include "psxhip_internal.h"
-
-int psxhip_ensure_device(int device);
 
 namespace {
 
@@ -193,14 +192,9 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
             if (pitch == 1) memcpy(dst, src, (size_t)samples_per_stream * sizeof(int16_t));
             else for (int k = 0; k < samples_per_stream; k++) dst[k] = src[(size_t)k * pitch];
             memset(dst + samples_per_stream, 0, (row - (size_t)samples_per_stream) * sizeof(int16_t));
-            a.chains[i].sample_offset = (int64_t)i * (int64_t)row;
-            a.chains[i].pitch = 1;
-            a.chains[i].sample_limit = samples_per_stream;
-            a.chains[i].n_units = n_units;
-            a.chains[i].unit_stride = 1;
-            a.unit_base[i] = i * n_units;
             a.states_in[i] = states[i];
         }
+        fill_planar_chains(a.chains, a.unit_base, n_streams, (int64_t)row, 1, samples_per_stream, n_units);
         a.samples = g_call.d_in();
         a.stage_elems = (int)(row * n_streams);
         a.n_chains = n_streams;
@@ -224,14 +218,7 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
     if (n_streams == 1) stream_stride = (int64_t)readable;        // a single stream needs no stride
     std::vector<psxhip_adpcm_chain_t> chains(n_streams);
     std::vector<int32_t> base(n_streams);
-    for (int i = 0; i < n_streams; i++) {
-        chains[i].sample_offset = (int64_t)i * (int64_t)per;
-        chains[i].pitch = pitch;
-        chains[i].sample_limit = samples_per_stream;
-        chains[i].n_units = n_units;
-        chains[i].unit_stride = 1;
-        base[i] = i * n_units;
-    }
+    fill_planar_chains(chains.data(), base.data(), n_streams, (int64_t)per, pitch, samples_per_stream, n_units);
     g_pool_device = device;
     DevBuf d_s(0), d_c(1), d_b(2), d_st(3), d_u(4), d_o(5);
     HIP_TRY(d_s.alloc(per * n_streams * sizeof(int16_t)), PSXHIP_ENOMEM);
@@ -289,14 +276,13 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
         psxhip_set_error("xa_encode_streams_host: bad argument");
         return PSXHIP_EINVAL;
     }
-    const int ch = stereo ? 2 : 1;
-    const int upg = bits == 4 ? 8 : 4;                         // units per 128-byte sound group
-    const int group_samples = upg * 28;                        // interleaved samples consumed per group (adpcm.c:301)
+    const XaLayout xa = xa_layout(format, stereo, bits);
+    const int ch = xa.channels;
+    const int group_samples = xa.units_per_group * 28;         // interleaved samples consumed per group (adpcm.c:301)
     const int64_t total = (int64_t)samples_per_stream * ch;    // adpcm.c:307-308
     const int groups = (int)((total + group_samples - 1) / group_samples);
     const int sectors = (groups + 17) / 18;                    // the loop runs until the sector is complete (adpcm.c:310)
-    const int ssz = format == 0 ? 2336 : 2352;
-    const int bytes = sectors * ssz;
+    const int bytes = sectors * xa.sector_bytes;
     if (n_streams == 0 || sectors == 0) return bytes;
     if (n_streams == 1) out_stride = bytes;
     if (out_stride < bytes) {
@@ -306,7 +292,7 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
     int rc = psxhip_ensure_device(device);
     if (rc) return rc;
 
-    const int units_per_stream = sectors * 18 * upg;
+    const int units_per_stream = sectors * xa.units_per_sector;
     const int units_per_chain = units_per_stream / ch;
     const size_t per = (size_t)total;
     if (n_streams == 1) stream_stride = (int64_t)per;             // a single stream needs no stride
@@ -322,15 +308,8 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
         const size_t row = (per + 7) & ~(size_t)7;
         memcpy(g_call.in(), samples, per * sizeof(int16_t));
         memset(g_call.in() + per, 0, (row - per) * sizeof(int16_t));
-        for (int c = 0; c < ch; c++) {
-            a.chains[c].sample_offset = c;
-            a.chains[c].pitch = ch;
-            a.chains[c].sample_limit = samples_per_stream;
-            a.chains[c].n_units = units_per_chain;
-            a.chains[c].unit_stride = ch;
-            a.unit_base[c] = c;
-            a.states_in[c] = states[c];
-        }
+        fill_interleaved_chains(a.chains, a.unit_base, 1, ch, 0, samples_per_stream, units_per_stream);
+        for (int c = 0; c < ch; c++) a.states_in[c] = states[c];
         a.samples = g_call.d_in();
         a.stage_elems = (int)row;
         a.n_chains = ch;
@@ -352,16 +331,7 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
     }
     std::vector<psxhip_adpcm_chain_t> chains((size_t)n_streams * ch);
     std::vector<int32_t> base((size_t)n_streams * ch);
-    for (int i = 0; i < n_streams; i++)
-        for (int c = 0; c < ch; c++) {
-            psxhip_adpcm_chain_t& d = chains[(size_t)i * ch + c];
-            d.sample_offset = (int64_t)i * (int64_t)per + c;
-            d.pitch = ch;
-            d.sample_limit = samples_per_stream;
-            d.n_units = units_per_chain;
-            d.unit_stride = ch;
-            base[(size_t)i * ch + c] = i * units_per_stream + c;
-        }
+    fill_interleaved_chains(chains.data(), base.data(), n_streams, ch, (int64_t)per, samples_per_stream, units_per_stream);
     std::vector<uint8_t> eof((size_t)n_streams * sectors, 0);
     if (eof_flags)
         memcpy(eof.data(), eof_flags, eof.size());
@@ -398,7 +368,7 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
         if (rc) return rc;
     }
     for (int i = 0; i < n_streams; i++) {
-        rc = psxhip_xa_assemble_device(device, d_u.as<uint8_t>() + (size_t)i * units_per_stream * PSXHIP_ADPCM_RECORD_SIZE(bits),
+        rc = psxhip_xa_assemble_device(device, d_u.as<uint8_t>() + (size_t)i * units_per_stream * xa.record_bytes,
                                        sectors, format, stereo, frequency, bits, file_number, channel_number,
                                        lbas ? lbas[i] : 0, d_e.as<uint8_t>() + (size_t)i * sectors,
                                        d_o.as<uint8_t>() + (size_t)i * bytes, st);

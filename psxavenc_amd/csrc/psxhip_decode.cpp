@@ -6,45 +6,23 @@
 
 #include <new>
 
+#include "device_buffer.h"
+#include "host_layout.h"
 #include "psxhip_decode_internal.h"
 #include "psxhip_internal.h"
 
-int psxhip_ensure_device(int device);
-
 struct psxhip_mdec_decoder {
     int device, width, height, nblk, wrap;
-    int16_t* d_ws = nullptr;          // levels of a call that wants pixels only
-    size_t ws_bytes = 0;
-    void* d_stage = nullptr;          // decode_frames_host: bitstreams, sizes, results, pixels
-    size_t stage_bytes = 0;
-    int16_t* d_stage_levels = nullptr;
-    size_t stage_levels_bytes = 0;
+    DeviceBuffer ws;                  // levels of a call that wants pixels only
+    DeviceBuffer stage;               // decode_frames_host: bitstreams, sizes, results, pixels
+    DeviceBuffer stage_levels;
 };
-
-namespace {
-
-int grow(void** p, size_t* have, size_t need) {
-    if (need <= *have) return PSXHIP_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(p, need), PSXHIP_ENOMEM);
-    *have = need;
-    return PSXHIP_OK;
-}
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-}  // namespace
 
 extern "C" const char* psxhip_mdec_decode_kernel_rev(void) { return PSXHIP_MDEC_DECODE_KERNEL_REV; }
 
 extern "C" void psxhip_mdec_decoder_destroy(psxhip_mdec_decoder_t* dec) {
     if (!dec) return;
     (void)hipSetDevice(dec->device);
-    if (dec->d_ws) (void)hipFree(dec->d_ws);
-    if (dec->d_stage) (void)hipFree(dec->d_stage);
-    if (dec->d_stage_levels) (void)hipFree(dec->d_stage_levels);
     delete dec;
 }
 
@@ -94,9 +72,9 @@ extern "C" int psxhip_mdec_decode_frames_device(psxhip_mdec_decoder_t* dec, cons
     HIP_TRY(hipSetDevice(dec->device), PSXHIP_EDEVICE);
     int16_t* levels = d_levels;
     if (!levels && d_frames) {
-        const int rc = grow((void**)&dec->d_ws, &dec->ws_bytes, (size_t)n_frames * dec->nblk * 64 * sizeof(int16_t));
+        const int rc = dec->ws.reserve((size_t)n_frames * dec->nblk * 64 * sizeof(int16_t));
         if (rc) return rc;
-        levels = dec->d_ws;
+        levels = dec->ws.as<int16_t>();
     }
     psxhip_mdec_parse_job_t pj;
     pj.d_bs = d_bs; pj.bs_stride = bs_stride; pj.d_sizes = d_bs_sizes; pj.uniform_size = uniform_size;
@@ -127,24 +105,26 @@ extern "C" int psxhip_mdec_decode_frames_host(psxhip_mdec_decoder_t* dec, const 
     const size_t n = (size_t)n_frames;
     const size_t row = (bs_stride + 3) & ~(size_t)3;                 // device rows are 4-byte aligned whatever the host's stride
     const size_t frame_bytes = (size_t)dec->width * dec->height * 3 / 2;
-    const size_t off_sizes = align256(n * row), off_dec = off_sizes + align256(n * sizeof(int32_t));
-    const size_t off_px = off_dec + align256(n * sizeof(psxhip_mdec_decoded_t));
-    int rc = grow(&dec->d_stage, &dec->stage_bytes, off_px + (frames ? n * frame_bytes : 0));
+    BumpOffsets o;
+    o.take(n * row);
+    const size_t off_sizes = o.take(n * sizeof(int32_t)), off_dec = o.take(n * sizeof(psxhip_mdec_decoded_t)), off_px = o.end;
+    int rc = dec->stage.reserve(off_px + (frames ? n * frame_bytes : 0));
     if (rc) return rc;
     const size_t level_bytes = n * dec->nblk * 64 * sizeof(int16_t);
-    if (levels && (rc = grow((void**)&dec->d_stage_levels, &dec->stage_levels_bytes, level_bytes))) return rc;
-    uint8_t* base = (uint8_t*)dec->d_stage;
+    if (levels && (rc = dec->stage_levels.reserve(level_bytes))) return rc;
+    uint8_t* base = dec->stage.as<uint8_t>();
+    int16_t* const d_levels = levels ? dec->stage_levels.as<int16_t>() : nullptr;
     if (row != bs_stride) HIP_TRY(hipMemset(base, 0, n * row), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpy2D(base, row, bs, bs_stride, bs_stride, n, hipMemcpyHostToDevice), PSXHIP_EDEVICE);
     if (bs_sizes) HIP_TRY(hipMemcpy(base + off_sizes, bs_sizes, n * sizeof(int32_t), hipMemcpyHostToDevice), PSXHIP_EDEVICE);
     // a frame that does not parse leaves its pixels untouched: they start from the caller's
     if (frames) HIP_TRY(hipMemcpy(base + off_px, frames, n * frame_bytes, hipMemcpyHostToDevice), PSXHIP_EDEVICE);
     rc = psxhip_mdec_decode_frames_device(dec, base, row, bs_sizes ? (const int32_t*)(base + off_sizes) : nullptr, uniform_size, n_frames,
-                                          levels ? dec->d_stage_levels : nullptr, frames ? base + off_px : nullptr, frame_bytes,
+                                          d_levels, frames ? base + off_px : nullptr, frame_bytes,
                                           (psxhip_mdec_decoded_t*)(base + off_dec), nullptr);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(decoded, base + off_dec, n * sizeof(psxhip_mdec_decoded_t), hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
-    if (levels) HIP_TRY(hipMemcpy(levels, dec->d_stage_levels, level_bytes, hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
+    if (levels) HIP_TRY(hipMemcpy(levels, d_levels, level_bytes, hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
     if (frames) HIP_TRY(hipMemcpy(frames, base + off_px, n * frame_bytes, hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
     HIP_TRY(hipDeviceSynchronize(), PSXHIP_EDEVICE);
     return PSXHIP_OK;

@@ -163,6 +163,14 @@ void psxhip_set_error(const char *fmt, ...);
 
 #ifdef __cplusplus
 }
+
+/* makes `device` current and its tables ready (psxhip_api.cpp); PSXHIP_OK, or the error with its text set */
+int psxhip_ensure_device(int device);
+/* the error every entry point ends with when the machine shows no GPU */
+static inline int psxhip_no_device(void) {
+	psxhip_set_error("no HIP device visible (libpsxav_hip has no CPU fallback)");
+	return PSXHIP_EDEVICE;
+}
 #endif
 
 /* a failed HIP call: its text goes to psxhip_last_error() and the calling function returns `code` */

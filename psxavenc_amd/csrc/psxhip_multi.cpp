@@ -214,10 +214,7 @@ extern "C" int psxhip_xa_encode_streams_host_multi(const int* devices, int n_dev
     }
     {   // (checked here, before any pointer is offset by a shard's first stream and before any thread is started)
         const int have = psxhip_device_count();
-        if (have <= 0) {
-            psxhip_set_error("no HIP device visible (libpsxav_hip has no CPU fallback)");
-            return PSXHIP_EDEVICE;
-        }
+        if (have <= 0) return psxhip_no_device();
         for (int i = 0; i < n_devices; i++)
             if (devices[i] < 0 || devices[i] >= have) {
                 psxhip_set_error("psxhip_xa_encode_streams_host_multi: device %d out of range (%d visible)", devices[i], have);

@@ -10,9 +10,8 @@
 #include <new>
 #include <vector>
 
+#include "device_buffer.h"
 #include "psxhip_internal.h"
-
-int psxhip_ensure_device(int device);
 
 namespace {
 
@@ -126,10 +125,7 @@ struct psxhip_resampler {
     int64_t consumed = 0;
     bool flushed = false;
     int coef_lds = 0, span = 0, grid_max = 1;
-    void* d_in = nullptr;            // convert_host's staging buffers, grown on demand
-    size_t in_bytes = 0;
-    int16_t* d_out = nullptr;
-    size_t out_bytes = 0;
+    DeviceBuffer d_in, d_out;        // convert_host's staging buffers, grown on demand
 };
 
 extern "C" const char* psxhip_resampler_kernel_rev(void) { return PSXHIP_AFE_KERNEL_REV; }
@@ -164,8 +160,6 @@ extern "C" void psxhip_resampler_destroy(psxhip_resampler_t* r) {
     (void)hipSetDevice(r->device);
     if (r->d_coef) (void)hipFree(r->d_coef);
     if (r->d_hist) (void)hipFree(r->d_hist);
-    if (r->d_in) (void)hipFree(r->d_in);
-    if (r->d_out) (void)hipFree(r->d_out);
     delete r;
 }
 
@@ -372,28 +366,17 @@ extern "C" int psxhip_resampler_convert_host(psxhip_resampler_t* r, const void* 
     for (int k = 0; n_in > 0 && k < nsrc; k++)
         if (!src[k]) return PSXHIP_EINVAL;
     HIP_TRY(hipSetDevice(r->device), PSXHIP_EDEVICE);
-    const size_t in_need = plane * nsrc, out_need = (size_t)count * r->dch * sizeof(int16_t);
-    if (in_need > r->in_bytes) {
-        if (r->d_in) (void)hipFree(r->d_in);
-        r->d_in = nullptr; r->in_bytes = 0;
-        HIP_TRY(hipMalloc(&r->d_in, in_need), PSXHIP_ENOMEM);
-        r->in_bytes = in_need;
-    }
-    if (out_need > r->out_bytes) {
-        if (r->d_out) (void)hipFree(r->d_out);
-        r->d_out = nullptr; r->out_bytes = 0;
-        HIP_TRY(hipMalloc((void**)&r->d_out, out_need), PSXHIP_ENOMEM);
-        r->out_bytes = out_need;
-    }
+    int rc;
+    if ((rc = r->d_in.reserve(plane * nsrc)) || (rc = r->d_out.reserve((size_t)count * r->dch * sizeof(int16_t)))) return rc;
     const void* p[8] = {};
     for (int k = 0; n_in > 0 && k < nsrc; k++) {
-        p[k] = (const char*)r->d_in + (size_t)k * plane;
+        p[k] = r->d_in.as<char>() + (size_t)k * plane;
         HIP_TRY(hipMemcpy((void*)p[k], src[k], plane, hipMemcpyHostToDevice), PSXHIP_EDEVICE);
     }
     int64_t got = 0;
-    const int rc = psxhip_resampler_convert_device(r, n_in > 0 ? p : nullptr, n_in, r->d_out, &got, flush, nullptr);
+    rc = psxhip_resampler_convert_device(r, n_in > 0 ? p : nullptr, n_in, r->d_out.as<int16_t>(), &got, flush, nullptr);
     if (rc) return rc;
-    if (got) HIP_TRY(hipMemcpy(dst, r->d_out, (size_t)got * r->dch * sizeof(int16_t), hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
+    if (got) HIP_TRY(hipMemcpy(dst, r->d_out.p, (size_t)got * r->dch * sizeof(int16_t), hipMemcpyDeviceToHost), PSXHIP_EDEVICE);
     HIP_TRY(hipDeviceSynchronize(), PSXHIP_EDEVICE);
     if (n_out) *n_out = got;
     return PSXHIP_OK;

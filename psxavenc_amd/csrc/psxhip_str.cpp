@@ -23,6 +23,8 @@
 #include "../../include/psxav_audio.h"
 #include "../../include/psxav_hip.h"
 #include "../../include/psxav_mdec.h"
+#include "device_buffer.h"
+#include "host_layout.h"
 #include "psxhip_internal.h"
 
 namespace {
@@ -55,7 +57,7 @@ struct psxhip_str_ctx {
     // ---- psxhip_str_encode_device: everything stays in HBM (device devices[0]).  Kept between calls with the same shape: the
     //      plan's tables on the device, the buffers the frames' bitstreams / unit records pass through, one encoder context, one
     //      ADPCM session over the caller's PCM, a stream + events for the audio leg
-    struct Dev {
+    struct __attribute__((visibility("hidden"))) Dev {
         psxhip_str_settings_t settings;
         int n_frames = -1, n_streams = 0;
         int64_t pcm_samples = -1;
@@ -64,8 +66,8 @@ struct psxhip_str_ctx {
         bool chunked = false;           // the XA tracks of the cached shape run as a speculate-and-verify session (else: serial chains)
         Plan plan;
         int n_vtab = 0, na = 0, nf = 0;
-        void *d_vtab = nullptr, *d_budgets = nullptr, *d_adst = nullptr, *d_eof = nullptr, *d_bs = nullptr, *d_res = nullptr, *d_units = nullptr;
-        void *d_chains = nullptr, *d_base = nullptr, *d_states = nullptr;      // short audio: the serial chains kernel's tables
+        struct { DeviceBuffer vtab, budgets, adst, eof, bs, res, units; } buf;      // of the cached shape: dropped together
+        struct { DeviceBuffer chains, base, states; } tab;                           // short audio: the serial chains kernel's tables
         psxhip_mdec_result_t* h_res = nullptr;                                 // page-locked
         psxhip_mdec_ctx_t* mdec = nullptr;
         int mdec_key[4] = {-1, -1, -1, -1};
@@ -232,8 +234,8 @@ void free_dev(psxhip_str_ctx* c) {
     if (d.astream) (void)hipStreamSynchronize(d.astream);
     if (d.session) psxhip_adpcm_session_destroy(d.session);
     if (d.mdec) psxhip_mdec_destroy(d.mdec);
-    void** bufs[] = {&d.d_vtab, &d.d_budgets, &d.d_adst, &d.d_eof, &d.d_bs, &d.d_res, &d.d_units, &d.d_chains, &d.d_base, &d.d_states};
-    for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    d.buf = {};
+    d.tab = {};
     if (d.h_res) (void)hipHostFree(d.h_res);
     if (d.ev_in) (void)hipEventDestroy(d.ev_in);
     if (d.ev_audio) (void)hipEventDestroy(d.ev_audio);
@@ -251,10 +253,7 @@ extern "C" int psxhip_str_create(psxhip_str_ctx_t** out, const int* devices, int
         return PSXHIP_EINVAL;
     }
     const int have = psxhip_device_count();
-    if (have <= 0) {
-        psxhip_set_error("no HIP device visible (libpsxav_hip has no CPU fallback)");
-        return PSXHIP_EDEVICE;
-    }
+    if (have <= 0) return psxhip_no_device();
     for (int i = 0; i < n_devices; i++)
         if (devices[i] < 0 || devices[i] >= have) {
             psxhip_set_error("psxhip_str_create: device %d out of range (%d visible)", devices[i], have);
@@ -371,7 +370,8 @@ extern "C" int psxhip_str_encode_host(psxhip_str_ctx_t* c, const psxhip_str_sett
     int rc_video = PSXHIP_OK;
     char err_video[256] = "";
     std::vector<uint8_t> xa_out;
-    const int at = s->format == FORMAT_STR ? 0x08 : (s->format == FORMAT_STRCD ? 0x18 : 0x00);     // mdec.c:822-829
+    int geo_size = 0, sub_at = 0, at = 0;                       // `at`: where a sector keeps its chunk header
+    (void)str_sector_geometry(s->format, &geo_size, &sub_at, &at);
     // Which frame slice / audio sector lands in which sector is in the plan; the sectors themselves (2 KiB of copying and a
     // 2 KiB EDC each) are built by a few threads, each on its own range.
     // `video`: build the video sectors of [n0, n1), else its audio sectors -- the two kinds are built by different threads at
@@ -515,15 +515,6 @@ extern "C" int psxhip_str_encode_host(psxhip_str_ctx_t* c, const psxhip_str_sett
 // bounds a single stream (its one tonal XA track is re-encoded serially for ~3 ms while the frames take 0.2) -- the video sectors
 // are built by a scatter kernel (sector header, subheaders, chunk header, 2016-byte slice, form-1 EDC) and the audio sectors are
 // assembled straight into their slots of the stream.  No PCIe, no host interleave.
-#define DEV_TRY(expr, code)                                                                          \
-    do {                                                                                             \
-        hipError_t e__ = (expr);                                                                     \
-        if (e__ != hipSuccess) {                                                                     \
-            psxhip_set_error("psxhip_str_encode_device: %s failed: %s", #expr, hipGetErrorString(e__)); \
-            return (code);                                                                           \
-        }                                                                                            \
-    } while (0)
-
 extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_settings_t* s, int n_streams, const uint8_t* d_frames,
                                         size_t frames_stream_stride, int n_frames, const int16_t* d_pcm, int64_t pcm_stream_stride,
                                         int64_t pcm_samples_per_channel, uint8_t* d_out, size_t out_stream_stride,
@@ -542,7 +533,7 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     std::lock_guard<std::mutex> call(c->mu);
     psxhip_str_ctx::Dev& d = c->dev;
     const int device = c->devices[0];
-    DEV_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
+    HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
     hipStream_t S = (hipStream_t)stream;
     // ---- the plan and its device tables: rebuilt when the shape of the job changes
     const bool same = d.n_frames == n_frames && d.pcm_samples == pcm_samples_per_channel && d.n_streams == n_streams && s &&
@@ -550,15 +541,15 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     if (!same) {
         Plan pl;
         memset(&pl.pub, 0, sizeof pl.pub);
-        const int rc = make_plan(s, n_frames, pcm_samples_per_channel, &pl);
+        int rc = make_plan(s, n_frames, pcm_samples_per_channel, &pl);
         if (rc) return rc;
         if (plan_out) *plan_out = pl.pub;
         // nothing of the old shape may still be running on the buffers that are about to go
-        DEV_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
-        if (d.astream) DEV_TRY(hipStreamSynchronize(d.astream), PSXHIP_EDEVICE);
+        HIP_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
+        if (d.astream) HIP_TRY(hipStreamSynchronize(d.astream), PSXHIP_EDEVICE);
         if (d.session) { psxhip_adpcm_session_destroy(d.session); d.session = nullptr; }
-        void** bufs[] = {&d.d_vtab, &d.d_budgets, &d.d_adst, &d.d_eof, &d.d_bs, &d.d_res, &d.d_units, &d.d_chains, &d.d_base, &d.d_states};
-        for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+        d.buf = {};
+        d.tab = {};
         if (d.h_res) { (void)hipHostFree(d.h_res); d.h_res = nullptr; }
         d.n_frames = -1;
         d.plan = pl;
@@ -585,27 +576,25 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         std::vector<int32_t> budgets((size_t)nf * n_streams);
         for (int i = 0; i < n_streams; i++)
             for (int f = 0; f < nf; f++) budgets[(size_t)i * nf + f] = pl.budgets[(size_t)f];
-        const int ch = s->audio_channels, upg = s->audio_bit_depth == 4 ? 8 : 4;
-        const size_t units_per_stream = (size_t)d.na * 18 * upg;
-        auto up = [&](void** dst, const void* src, size_t bytes) -> hipError_t {
-            hipError_t e = hipMalloc(dst, bytes ? bytes : 4);
-            if (e == hipSuccess && bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-            return e;
+        const size_t units_per_stream = (size_t)d.na * xa_layout(s->format == FORMAT_STRCD, s->audio_channels == 2, s->audio_bit_depth).units_per_sector;
+        auto up = [](DeviceBuffer& dst, const void* src, size_t bytes) -> int {
+            const int rc = dst.reserve(bytes ? bytes : 4);
+            if (rc) return rc;
+            if (bytes) HIP_TRY(hipMemcpy(dst.p, src, bytes, hipMemcpyHostToDevice), PSXHIP_EDEVICE);
+            return PSXHIP_OK;
         };
-        DEV_TRY(up(&d.d_vtab, vtab.data(), vtab.size() * 4), PSXHIP_ENOMEM);
-        DEV_TRY(up(&d.d_budgets, budgets.data(), budgets.size() * 4), PSXHIP_ENOMEM);
-        DEV_TRY(up(&d.d_adst, adst.data(), adst.size() * 4), PSXHIP_ENOMEM);
-        DEV_TRY(up(&d.d_eof, eof.data(), eof.size()), PSXHIP_ENOMEM);
         const size_t bs_bytes = ostride * (size_t)nf * n_streams + 16;          // (never an empty allocation: a stream may hold no frame at all)
-        DEV_TRY(hipMalloc(&d.d_bs, bs_bytes), PSXHIP_ENOMEM);
-        DEV_TRY(hipMemset(d.d_bs, 0, bs_bytes), PSXHIP_EDEVICE);      // (rows wider than a frame's own budget read as zero there)
-        DEV_TRY(hipMalloc(&d.d_res, sizeof(psxhip_mdec_result_t) * (size_t)(nf ? nf : 1) * n_streams), PSXHIP_ENOMEM);
-        DEV_TRY(hipHostMalloc((void**)&d.h_res, sizeof(psxhip_mdec_result_t) * (size_t)(nf ? nf : 1) * n_streams, hipHostMallocDefault), PSXHIP_ENOMEM);
-        DEV_TRY(hipMalloc(&d.d_units, (units_per_stream ? units_per_stream : 1) * PSXHIP_ADPCM_RECORD_BYTES * n_streams), PSXHIP_ENOMEM);
-        if (!d.astream) DEV_TRY(hipStreamCreateWithFlags(&d.astream, hipStreamNonBlocking), PSXHIP_EDEVICE);
-        if (!d.ev_in) DEV_TRY(hipEventCreateWithFlags(&d.ev_in, hipEventDisableTiming), PSXHIP_EDEVICE);
-        if (!d.ev_audio) DEV_TRY(hipEventCreateWithFlags(&d.ev_audio, hipEventDisableTiming), PSXHIP_EDEVICE);
-        (void)ch;
+        const size_t res_bytes = sizeof(psxhip_mdec_result_t) * (size_t)(nf ? nf : 1) * n_streams;
+        if ((rc = up(d.buf.vtab, vtab.data(), vtab.size() * 4)) || (rc = up(d.buf.budgets, budgets.data(), budgets.size() * 4)) ||
+            (rc = up(d.buf.adst, adst.data(), adst.size() * 4)) || (rc = up(d.buf.eof, eof.data(), eof.size())) || (rc = d.buf.bs.reserve(bs_bytes)))
+            return rc;
+        HIP_TRY(hipMemset(d.buf.bs.p, 0, bs_bytes), PSXHIP_EDEVICE);      // (rows wider than a frame's own budget read as zero there)
+        if ((rc = d.buf.res.reserve(res_bytes))) return rc;
+        HIP_TRY(hipHostMalloc((void**)&d.h_res, res_bytes, hipHostMallocDefault), PSXHIP_ENOMEM);
+        if ((rc = d.buf.units.reserve((units_per_stream ? units_per_stream : 1) * PSXHIP_ADPCM_RECORD_BYTES * n_streams))) return rc;
+        if (!d.astream) HIP_TRY(hipStreamCreateWithFlags(&d.astream, hipStreamNonBlocking), PSXHIP_EDEVICE);
+        if (!d.ev_in) HIP_TRY(hipEventCreateWithFlags(&d.ev_in, hipEventDisableTiming), PSXHIP_EDEVICE);
+        if (!d.ev_audio) HIP_TRY(hipEventCreateWithFlags(&d.ev_audio, hipEventDisableTiming), PSXHIP_EDEVICE);
         d.n_frames = n_frames;
         d.pcm_samples = pcm_samples_per_channel;
         d.n_streams = n_streams;
@@ -642,19 +631,19 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             b.d_frames = d_frames + (size_t)i * frames_stream_stride;
             b.n_frames = contiguous ? nf * n_streams : nf;
             b.reserved = 0;
-            b.d_frame_max_sizes = (const int32_t*)d.d_budgets + (size_t)i * nf;
-            b.d_out = (uint8_t*)d.d_bs + (size_t)i * nf * ostride;
-            b.d_results = (psxhip_mdec_result_t*)d.d_res + (size_t)i * nf;
+            b.d_frame_max_sizes = d.buf.budgets.as<const int32_t>() + (size_t)i * nf;
+            b.d_out = d.buf.bs.as<uint8_t>() + (size_t)i * nf * ostride;
+            b.d_results = d.buf.res.as<psxhip_mdec_result_t>() + (size_t)i * nf;
             batches.push_back(b);
         }
         int rc = psxhip_mdec_encode_batches_device(d.mdec, batches.data(), (int)batches.size(), fsz, 0, ostride, S);
         if (rc) return rc;
-        vj.d_bs = (const uint8_t*)d.d_bs;
+        vj.d_bs = d.buf.bs.as<const uint8_t>();
         vj.bs_stride = ostride;
         vj.bs_stream_stride = ostride * (size_t)nf;
-        vj.d_res = (const psxhip_mdec_result_t*)d.d_res;
+        vj.d_res = d.buf.res.as<const psxhip_mdec_result_t>();
         vj.frames_per_stream = nf;
-        vj.d_tab = (const int32_t*)d.d_vtab;
+        vj.d_tab = d.buf.vtab.as<const int32_t>();
         vj.n_entries = d.n_vtab;
         vj.n_streams = n_streams;
         vj.format = s->format;
@@ -668,10 +657,10 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         vj.out_stream_stride = out_stream_stride;
         rc = psxhip_str_video_sectors_launch(device, &vj, S);
         if (rc) return rc;
-        DEV_TRY(hipMemcpyAsync(d.h_res, d.d_res, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d.h_res, d.buf.res.p, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
     } else if (d.n_vtab) {
         // no frame in the stream, but audio slots without samples: zero sectors (nothing reads a bitstream)
-        vj.d_bs = (const uint8_t*)d.d_bs; vj.d_res = (const psxhip_mdec_result_t*)d.d_res; vj.d_tab = (const int32_t*)d.d_vtab;
+        vj.d_bs = d.buf.bs.as<const uint8_t>(); vj.d_res = d.buf.res.as<const psxhip_mdec_result_t>(); vj.d_tab = d.buf.vtab.as<const int32_t>();
         vj.n_entries = d.n_vtab; vj.n_streams = n_streams; vj.format = s->format; vj.sector_size = (int)ssz; vj.d_out = d_out;
         vj.out_stream_stride = out_stream_stride;
         const int rc = psxhip_str_video_sectors_launch(device, &vj, S);
@@ -681,16 +670,17 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     // ---- audio: the streams' XA tracks as chains of one session on the handle's own stream, behind the caller's inputs; the
     //      host drives the verify passes (the call is synchronous), the video leg above runs meanwhile
     if (na) {
-        const int ch = s->audio_channels, bits = s->audio_bit_depth, upg = bits == 4 ? 8 : 4;
-        const int units_per_stream = na * 18 * upg, units_per_chain = units_per_stream / ch;
+        const int ch = s->audio_channels, bits = s->audio_bit_depth;
+        const XaLayout xa = xa_layout(s->format == FORMAT_STRCD, ch == 2, bits);
+        const int units_per_stream = na * xa.units_per_sector, units_per_chain = units_per_stream / ch;
         const int64_t need = pl.audio_samples;                                   // per channel, over the whole stream
         const int limit = (int)(pcm_samples_per_channel < need ? pcm_samples_per_channel : need);      // past it the encoder reads zeros (decoding.c:521-527)
         if (n_streams > 1 && pcm_stream_stride < (int64_t)limit * ch) {
             psxhip_set_error("psxhip_str_encode_device: pcm_stream_stride smaller than a stream's samples");
             return PSXHIP_EINVAL;
         }
-        DEV_TRY(hipEventRecord(d.ev_in, S), PSXHIP_EDEVICE);
-        DEV_TRY(hipStreamWaitEvent(d.astream, d.ev_in, 0), PSXHIP_EDEVICE);
+        HIP_TRY(hipEventRecord(d.ev_in, S), PSXHIP_EDEVICE);
+        HIP_TRY(hipStreamWaitEvent(d.astream, d.ev_in, 0), PSXHIP_EDEVICE);
         const int n_chains = n_streams * ch;
         const bool chunked = units_per_chain >= psxhip_adpcm_chunked_threshold(n_chains);      // (the rule of the host entry points)
         // an error from here on leaves nothing of this call in flight on the caller's buffers
@@ -700,33 +690,21 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             if (d.session) { psxhip_adpcm_session_destroy(d.session); d.session = nullptr; }
             std::vector<psxhip_adpcm_chain_t> chains((size_t)n_chains);
             std::vector<int32_t> base((size_t)n_chains);
-            for (int i = 0; i < n_streams; i++)
-                for (int k = 0; k < ch; k++) {
-                    psxhip_adpcm_chain_t& cd = chains[(size_t)i * ch + k];
-                    cd.sample_offset = (int64_t)i * pcm_stream_stride + k;
-                    cd.pitch = ch;
-                    cd.sample_limit = limit;
-                    cd.n_units = units_per_chain;
-                    cd.unit_stride = ch;
-                    base[(size_t)i * ch + k] = i * units_per_stream + k;
-                }
+            fill_interleaved_chains(chains.data(), base.data(), n_streams, ch, pcm_stream_stride, limit, units_per_stream);
             if (chunked) {
                 int chunk_units = 0, warmup_units = 0;
                 psxhip_adpcm_pick_chunking((long long)units_per_chain * n_chains, 5, device, &chunk_units, &warmup_units);
                 const int rc = psxhip_adpcm_session_create(&d.session, device, d_pcm, chains.data(), base.data(), nullptr, n_chains, 4, bits,
-                                                           (uint8_t*)d.d_units, chunk_units, warmup_units, d.astream);
+                                                           d.buf.units.as<uint8_t>(), chunk_units, warmup_units, d.astream);
                 if (rc) return fail(rc);
             } else {
-                void** bufs[] = {&d.d_chains, &d.d_base, &d.d_states};
-                for (void** b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
-                if (hipMalloc(&d.d_chains, chains.size() * sizeof(chains[0])) != hipSuccess || hipMalloc(&d.d_base, base.size() * 4) != hipSuccess ||
-                    hipMalloc(&d.d_states, chains.size() * sizeof(psxhip_adpcm_state_t)) != hipSuccess) {
-                    (void)hipGetLastError();
-                    psxhip_set_error("psxhip_str_encode_device: out of device memory (chain tables)");
-                    return fail(PSXHIP_ENOMEM);
-                }
-                if (hipMemcpy(d.d_chains, chains.data(), chains.size() * sizeof(chains[0]), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(d.d_base, base.data(), base.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+                d.tab = {};
+                int rc;
+                if ((rc = d.tab.chains.reserve(chains.size() * sizeof(chains[0]))) || (rc = d.tab.base.reserve(base.size() * 4)) ||
+                    (rc = d.tab.states.reserve(chains.size() * sizeof(psxhip_adpcm_state_t))))
+                    return fail(rc);
+                if (hipMemcpy(d.tab.chains.p, chains.data(), chains.size() * sizeof(chains[0]), hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(d.tab.base.p, base.data(), base.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
                     psxhip_set_error("psxhip_str_encode_device: chain tables: %s", hipGetErrorString(hipGetLastError()));
                     return fail(PSXHIP_EDEVICE);
                 }
@@ -743,19 +721,19 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             rc = psxhip_adpcm_session_run(d.session, zero.data(), nullptr, 0, nullptr, nullptr);
             if (rc < 0) return fail(rc);
         } else {
-            DEV_TRY(hipMemsetAsync(d.d_states, 0, (size_t)n_chains * sizeof(psxhip_adpcm_state_t), d.astream), PSXHIP_EDEVICE);
-            rc = psxhip_adpcm_encode_chains_device(device, d_pcm, (const psxhip_adpcm_chain_t*)d.d_chains, (const int32_t*)d.d_base, n_chains, 4,
-                                                   bits, (psxhip_adpcm_state_t*)d.d_states, (uint8_t*)d.d_units, d.astream);
+            HIP_TRY(hipMemsetAsync(d.tab.states.p, 0, (size_t)n_chains * sizeof(psxhip_adpcm_state_t), d.astream), PSXHIP_EDEVICE);
+            rc = psxhip_adpcm_encode_chains_device(device, d_pcm, d.tab.chains.as<const psxhip_adpcm_chain_t>(), d.tab.base.as<const int32_t>(), n_chains, 4,
+                                                   bits, d.tab.states.as<psxhip_adpcm_state_t>(), d.buf.units.as<uint8_t>(), d.astream);
             if (rc) return fail(rc);
         }
-        rc = psxhip_xa_assemble_scatter(device, (const uint8_t*)d.d_units, na, s->format == FORMAT_STRCD ? 1 : 0, ch == 2, s->audio_frequency, bits,
-                                        s->audio_xa_file, s->audio_xa_channel, 0, (const uint8_t*)d.d_eof, 0u, d_out, (const int32_t*)d.d_adst,
-                                        n_streams, (size_t)units_per_stream * PSXHIP_ADPCM_RECORD_SIZE(bits), out_stream_stride, d.astream);
+        rc = psxhip_xa_assemble_scatter(device, d.buf.units.as<const uint8_t>(), na, s->format == FORMAT_STRCD ? 1 : 0, ch == 2, s->audio_frequency, bits,
+                                        s->audio_xa_file, s->audio_xa_channel, 0, d.buf.eof.as<const uint8_t>(), 0u, d_out, d.buf.adst.as<const int32_t>(),
+                                        n_streams, (size_t)units_per_stream * xa.record_bytes, out_stream_stride, d.astream);
         if (rc) return fail(rc);
-        DEV_TRY(hipEventRecord(d.ev_audio, d.astream), PSXHIP_EDEVICE);
-        DEV_TRY(hipStreamWaitEvent(S, d.ev_audio, 0), PSXHIP_EDEVICE);
+        HIP_TRY(hipEventRecord(d.ev_audio, d.astream), PSXHIP_EDEVICE);
+        HIP_TRY(hipStreamWaitEvent(S, d.ev_audio, 0), PSXHIP_EDEVICE);
     }
-    DEV_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
+    HIP_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
     if (nf) {
         // frames the split kernel's watchdog released (another process held the CUs): encoded again through the frame kernel, and
         // the video sectors built again over them
@@ -766,9 +744,9 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
                 b.d_frames = d_frames + (i / (size_t)nf) * frames_stream_stride + (i % (size_t)nf) * fsz;
                 b.n_frames = 1;
                 b.reserved = 0;
-                b.d_frame_max_sizes = (const int32_t*)d.d_budgets + i;
-                b.d_out = (uint8_t*)d.d_bs + i * ostride;
-                b.d_results = (psxhip_mdec_result_t*)d.d_res + i;
+                b.d_frame_max_sizes = d.buf.budgets.as<const int32_t>() + i;
+                b.d_out = d.buf.bs.as<uint8_t>() + i * ostride;
+                b.d_results = d.buf.res.as<psxhip_mdec_result_t>() + i;
                 again.push_back(b);
             }
         if (!again.empty()) {
@@ -776,8 +754,8 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             if (rc) return rc;
             rc = psxhip_str_video_sectors_launch(device, &vj, S);
             if (rc) return rc;
-            DEV_TRY(hipMemcpyAsync(d.h_res, d.d_res, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
-            DEV_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
+            HIP_TRY(hipMemcpyAsync(d.h_res, d.buf.res.p, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
+            HIP_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
         }
     }
     long long qsum = 0;
@@ -791,4 +769,3 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     if (plan_out) plan_out->quant_scale_sum = qsum;
     return PSXHIP_OK;
 }
-#undef DEV_TRY

@@ -9,43 +9,20 @@
 #include <new>
 
 #include "../../include/psxav_audio.h"
+#include "device_buffer.h"
+#include "host_layout.h"
 #include "psxhip_internal.h"
 #include "psxhip_str_demux_internal.h"
 
-int psxhip_ensure_device(int device);
-
 struct psxhip_str_reader {
     int device = 0;
-    void* d_ws = nullptr;             // psxhip_str_demux_device: the workspace of psxhip_str_demux_job_t
-    size_t ws_bytes = 0;
-    void* d_stage = nullptr;          // psxhip_str_read_host: sectors, rows, records, XA sectors, unit records, PCM, pictures
-    size_t stage_bytes = 0;
+    DeviceBuffer ws;                  // psxhip_str_demux_device: the workspace of psxhip_str_demux_job_t
+    DeviceBuffer stage;               // psxhip_str_read_host: sectors, rows, records, XA sectors, unit records, PCM, pictures
     psxhip_mdec_decoder_t* dec = nullptr;
     int dec_key[3] = {-1, -1, -1};    // width, height, dc_wrap
 };
 
 namespace {
-
-int grow(void** p, size_t* have, size_t need) {
-    if (need <= *have) return PSXHIP_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(p, need), PSXHIP_ENOMEM);
-    *have = need;
-    return PSXHIP_OK;
-}
-
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-bool geometry_of(int format, int* sector_size, int* sub_at, int* hdr_at) {      // mdec.c:822-829
-    switch (format) {
-    case 6: *sector_size = 2336; *sub_at = 0; *hdr_at = 0x08; return true;
-    case 7: *sector_size = 2352; *sub_at = 0x10; *hdr_at = 0x18; return true;
-    case 9: *sector_size = 2048; *sub_at = -1; *hdr_at = 0x00; return true;
-    }
-    return false;
-}
 
 bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
 
@@ -69,8 +46,6 @@ extern "C" void psxhip_str_reader_destroy(psxhip_str_reader_t* r) {
     if (!r) return;
     (void)hipSetDevice(r->device);
     if (r->dec) psxhip_mdec_decoder_destroy(r->dec);
-    if (r->d_ws) (void)hipFree(r->d_ws);
-    if (r->d_stage) (void)hipFree(r->d_stage);
     delete r;
 }
 
@@ -81,7 +56,7 @@ extern "C" int psxhip_str_demux_device(psxhip_str_reader_t* reader, const psxhip
                                        psxhip_str_summary_t* d_summary, void* stream) {
     psxhip_str_demux_job_t j;
     memset(&j, 0, sizeof j);
-    if (!s || !geometry_of(s->format, &j.sector_size, &j.sub_at, &j.hdr_at)) {
+    if (!s || !str_sector_geometry(s->format, &j.sector_size, &j.sub_at, &j.hdr_at)) {
         psxhip_set_error("psxhip_str_demux_device: NULL settings, or a format that is none of 6 (STR), 7 (STRCD), 9 (STRV)");
         return PSXHIP_EINVAL;
     }
@@ -103,10 +78,7 @@ extern "C" int psxhip_str_demux_device(psxhip_str_reader_t* reader, const psxhip
         psxhip_set_error("psxhip_str_demux_device: a stream stride smaller than a stream");
         return PSXHIP_EINVAL;
     }
-    if (psxhip_device_count() <= 0) {
-        psxhip_set_error("no HIP device visible (libpsxav_hip has no CPU fallback)");
-        return PSXHIP_EDEVICE;
-    }
+    if (psxhip_device_count() <= 0) return psxhip_no_device();
     if (!reader) {
         psxhip_set_error("psxhip_str_demux_device: NULL handle");
         return PSXHIP_EINVAL;
@@ -117,12 +89,13 @@ extern "C" int psxhip_str_demux_device(psxhip_str_reader_t* reader, const psxhip
     const size_t S = (size_t)n_streams, n = (size_t)n_sectors, rows = S * (size_t)max_frames;
     const size_t n_blocks = (n + PSXHIP_STR_DEMUX_SCAN_BLOCK - 1) / PSXHIP_STR_DEMUX_SCAN_BLOCK;
     // the workspace: d_owner, d_lead and d_min back to back (one fill with ones)
-    const size_t o_rec = 0, o_table = o_rec + align256(S * n * 16), o_blocks = o_table + align256(S * n * sizeof(psxhip_str_sector_t));
-    const size_t o_owner = o_blocks + align256(S * n_blocks * 4), o_lead = o_owner + rows * cap * 4, o_min = o_lead + rows * 4;
-    const size_t o_status = align256(o_min + S * 4), bytes = o_status + align256(rows * 4);
-    const int rc = grow(&reader->d_ws, &reader->ws_bytes, bytes);
+    BumpOffsets o;
+    const size_t o_rec = o.take(S * n * 16), o_table = o.take(S * n * sizeof(psxhip_str_sector_t)), o_blocks = o.take(S * n_blocks * 4);
+    const size_t o_owner = o.take(rows * cap * 4 + rows * 4 + S * 4), o_lead = o_owner + rows * cap * 4, o_min = o_lead + rows * 4;
+    const size_t o_status = o.take(rows * 4);
+    const int rc = reader->ws.reserve(o.end);
     if (rc) return rc;
-    uint8_t* const ws = (uint8_t*)reader->d_ws;
+    uint8_t* const ws = reader->ws.as<uint8_t>();
 
     j.format = s->format;
     j.audio_on = j.sub_at >= 0 && s->audio_channels != 0;
@@ -164,7 +137,7 @@ extern "C" int psxhip_str_read_host(psxhip_str_reader_t* reader, const psxhip_st
                                     psxhip_mdec_decoded_t* decoded, int16_t* pcm, int64_t pcm_capacity, int32_t* xa_sector_status,
                                     psxhip_str_summary_t* summary) {
     int ssz_i = 0, sub_at = 0, hdr_at = 0;
-    if (!s || !geometry_of(s->format, &ssz_i, &sub_at, &hdr_at)) {
+    if (!s || !str_sector_geometry(s->format, &ssz_i, &sub_at, &hdr_at)) {
         psxhip_set_error("psxhip_str_read_host: NULL settings, or a format that is none of 6 (STR), 7 (STRCD), 9 (STRV)");
         return PSXHIP_EINVAL;
     }
@@ -193,10 +166,7 @@ extern "C" int psxhip_str_read_host(psxhip_str_reader_t* reader, const psxhip_st
         psxhip_set_error("psxhip_str_read_host: the frame rate and CD speed give a frame %lld chunks", chunks);
         return PSXHIP_EINVAL;
     }
-    if (psxhip_device_count() <= 0) {
-        psxhip_set_error("no HIP device visible (libpsxav_hip has no CPU fallback)");
-        return PSXHIP_EDEVICE;
-    }
+    if (psxhip_device_count() <= 0) return psxhip_no_device();
     if (!reader) {
         psxhip_set_error("psxhip_str_read_host: NULL handle");
         return PSXHIP_EINVAL;
@@ -214,18 +184,20 @@ extern "C" int psxhip_str_read_host(psxhip_str_reader_t* reader, const psxhip_st
     }
     const size_t ssz = (size_t)ssz_i, n = (size_t)n_sectors, mf = (size_t)max_frames, bs_stride = (size_t)chunks * 2016;
     const size_t frame_bytes = (size_t)s->video_width * s->video_height * 3 / 2;
-    const int bits = s->audio_bit_depth, upg = bits == 4 ? 8 : 4;
-    const size_t sector_elems = bits == 4 ? 4032 : 2016;                 // int16 per XA sector, both channels together
+    const int bits = s->audio_bit_depth;
+    const XaLayout xa = xa_layout(s->format == 7 ? 1 : 0, ch == 2, bits);
+    const size_t sector_elems = (size_t)xa.samples_per_sector;
     size_t xa_cap = 0;
     if (pcm && ch && sub_at >= 0) xa_cap = (size_t)pcm_capacity / sector_elems < n ? (size_t)pcm_capacity / sector_elems : n;
-    const size_t rec = (size_t)PSXHIP_ADPCM_RECORD_SIZE(bits);
-    const size_t o_sec = 0, o_bs = o_sec + align256(n * ssz), o_sizes = o_bs + align256(mf * bs_stride), o_info = o_sizes + align256(mf * 4);
-    const size_t o_dec = o_info + align256(mf * sizeof(psxhip_str_frame_info_t)), o_sum = o_dec + align256(mf * sizeof(psxhip_mdec_decoded_t));
-    const size_t o_xa = o_sum + 256, o_units = o_xa + align256(xa_cap * ssz), o_xst = o_units + align256(xa_cap * 18 * upg * rec);
-    const size_t o_states = o_xst + align256(xa_cap * 4), o_pcm = o_states + 256, o_px = o_pcm + align256(xa_cap * sector_elems * 2);
-    int rc = grow(&reader->d_stage, &reader->stage_bytes, o_px + (frames ? mf * frame_bytes : 0) + 256);
+    BumpOffsets o;
+    const size_t o_sec = o.take(n * ssz), o_bs = o.take(mf * bs_stride), o_sizes = o.take(mf * 4);
+    const size_t o_info = o.take(mf * sizeof(psxhip_str_frame_info_t)), o_dec = o.take(mf * sizeof(psxhip_mdec_decoded_t));
+    const size_t o_sum = o.take(sizeof(psxhip_str_summary_t)), o_xa = o.take(xa_cap * ssz);
+    const size_t o_units = o.take(xa_cap * xa.units_per_sector * xa.record_bytes), o_xst = o.take(xa_cap * 4);
+    const size_t o_states = o.take(sizeof(psxhip_adpcm_state_t) * 2), o_pcm = o.take(xa_cap * sector_elems * 2), o_px = o.end;
+    int rc = reader->stage.reserve(o_px + (frames ? mf * frame_bytes : 0) + 256);
     if (rc) return rc;
-    uint8_t* const d = (uint8_t*)reader->d_stage;
+    uint8_t* const d = reader->stage.as<uint8_t>();
     hipStream_t st = nullptr;
     if (n) HIP_TRY(hipMemcpyAsync(d + o_sec, sectors, n * ssz, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     if (mf) HIP_TRY(hipMemsetAsync(d + o_bs, 0, mf * bs_stride, st), PSXHIP_EDEVICE);       // row bytes no chunk covers read as zero
@@ -244,20 +216,13 @@ extern "C" int psxhip_str_read_host(psxhip_str_reader_t* reader, const psxhip_st
     }
     const size_t na = (size_t)summary->n_audio < xa_cap ? (size_t)summary->n_audio : xa_cap;
     if (na) {
-        rc = psxhip_xa_disassemble_device(reader->device, d + o_xa, (int)na, s->format == 7 ? 1 : 0, ch == 2, s->audio_frequency, bits, d + o_units,
+        rc = psxhip_xa_disassemble_device(reader->device, d + o_xa, (int)na, s->format == 7, ch == 2, s->audio_frequency, bits, d + o_units,
                                           (int32_t*)(d + o_xst), st);
         if (rc) return rc;
-        const int units = (int)(na * 18 * upg), per_chain = units / ch;
+        const int units = (int)na * xa.units_per_sector;
         psxhip_adpcm_chain_t chains[2];
         int32_t unit_base[2];
-        for (int c = 0; c < ch; c++) {
-            chains[c].sample_offset = c;
-            chains[c].pitch = ch;
-            chains[c].sample_limit = per_chain * 28;
-            chains[c].n_units = per_chain;
-            chains[c].unit_stride = ch;
-            unit_base[c] = c;
-        }
+        fill_interleaved_chains(chains, unit_base, 1, ch, 0, units / ch * 28, units);
         HIP_TRY(hipMemsetAsync(d + o_states, 0, sizeof(psxhip_adpcm_state_t) * 2, st), PSXHIP_EDEVICE);
         rc = psxhip_adpcm_decode_chains_chunked(reader->device, d + o_units, chains, unit_base, ch, 4, bits, (psxhip_adpcm_state_t*)(d + o_states),
                                                 (int16_t*)(d + o_pcm), nullptr, nullptr, 0, -1, 0, st);

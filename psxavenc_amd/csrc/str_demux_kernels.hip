@@ -284,8 +284,6 @@ __global__ __launch_bounds__(256) void str_demux_finish_kernel(const psxhip_str_
 
 }  // namespace
 
-int psxhip_ensure_device(int device);
-
 extern "C" int psxhip_str_demux_launch(int device, const psxhip_str_demux_job_t* j, void* stream) {
     int rc = psxhip_ensure_device(device);
     if (rc) return rc;

@@ -86,8 +86,6 @@ __global__ void synth_pcm_kernel(int16_t* pcm, uint32_t seed, uint32_t chain, lo
 
 }  // namespace
 
-int psxhip_ensure_device(int device);
-
 extern "C" int psxhip_synth_frames_device(int device, uint8_t* d_frames, size_t frame_stride, int width, int height,
                                           uint32_t seed, uint32_t first_frame, int n_frames, int noise_amp, void* stream) {
     if (!d_frames || width <= 0 || height <= 0 || (width % 16) || (height % 16) || n_frames < 0 || (frame_stride & 3) ||

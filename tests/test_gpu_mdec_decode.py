@@ -187,6 +187,29 @@ def test_null_outputs_and_host_entry_point(oracle, torch):
     dec.close()
 
 
+def test_host_entry_point_small_larger_small_on_one_handle(oracle, torch):
+    """1, then 5, then 1 frame through decode_frames_host of ONE decoder, with and without pixels: the handle's staging buffers are
+    allocated, outgrown and reused; each call against the oracle's reader and the numpy reconstruction"""
+    from psxavenc_amd import MdecDecoder
+    w, h, budget = 32, 16, 1024
+    fr = oracle.synth_frames(w, h, 7, seed=21, amp=8)
+    rows, res, rc = oracle.mdec_encode(0, w, h, fr, budget)
+    assert rc == 0 and (res[:, 0] <= 63).all()
+    want = [DC.oracle_decode(DC.Case("", w, h, False, rows[i], budget)) for i in range(7)]
+    dec = MdecDecoder(w, h, dc_wrap=False)
+    for pixels in (True, False, True):
+        for lo, hi in ((0, 1), (1, 6), (6, 7)):
+            hl, hp, hr = dec.decode_frames_host(rows[lo:hi], budget, frames=pixels)
+            assert (hp is None) == (not pixels)
+            for i in range(lo, hi):
+                rc, levels, q, v, nbits = want[i]
+                assert rc == 0 and tuple(hr[i - lo]) == (0, q, v, nbits), (pixels, lo, i)
+                assert np.array_equal(hl[i - lo], levels), (pixels, lo, i)
+                if pixels:
+                    assert np.array_equal(hp[i - lo], R.reconstruct(w, h, levels, q)), (pixels, lo, i)
+    dec.close()
+
+
 def test_corrupted_corpus_on_the_device(oracle, torch, sim):  # noqa: F811
     """status against the oracle, guard bytes intact; run once, after the CPU run of the same corpus"""
     from psxavenc_amd import MdecDecoder

@@ -155,6 +155,24 @@ def test_random_chunking_equals_one_call_host_equals_device_and_reset_repeats():
         r.close()
 
 
+def test_convert_host_small_larger_small_on_one_handle():
+    """pieces of 100, 20000 and 100 input frames through convert_host of ONE handle: its staging buffers are allocated, outgrown and
+    reused; the pieces' outputs are the statement's over the concatenation"""
+    rs = _res()
+    fmt, sch, dch, src, dst = 0, 2, 2, 44100, 37800
+    pieces = [100, 20000, 100]
+    x = _source(fmt, sch, sum(pieces), 5)
+    want = _want(fmt, x, sch, src, dst, dch, None)
+    r = rs.Resampler(fmt, sch, src, dch, dst)
+    outs, done = [], 0
+    for j, n in enumerate(pieces):
+        outs.append(r.convert_host(np.ascontiguousarray(x[done:done + n]), flush=j == len(pieces) - 1))
+        done += n
+    assert all(o.shape[0] > 0 for o in outs)
+    assert np.array_equal(np.concatenate(outs), want)
+    r.close()
+
+
 def test_chain_48k_f32p_in_hbm_to_the_device_str_muxer():
     """decoded 48 kHz stereo float in HBM -> resampler -> psxhip_str_encode_device (STRCD): the sectors equal encode_file_str over
     the reference's own XA encoder fed the statement's PCM"""

@@ -211,11 +211,25 @@ def test_targeted_edits(fmt, channels):
             assert ((got["info"][:, 7] & (D.RANGE | D.MISSING)) == (D.RANGE | D.MISSING)).all() and not got["sizes"].any()
 
 
+def _expected_read(s, dec, stream, nf, stride):
+    """what StrReader.read(s, stream, nf, first_frame=1) over pictures of 0x55 has to return: the statement's demux, then this
+    library's BS decoder and XA decoder (each held to its own reference in its own file) over what the statement found"""
+    import torch
+    from psxavenc_amd import xa_decode_streams
+    from psxavenc_amd.adpcm import XaSettings
+    bs, xa = np.zeros((nf, stride), np.uint8), np.zeros((stream.shape[0], stream.shape[1]), np.uint8)
+    want = D.demux(s, stream, 1, nf, bs, xa)
+    canvas = torch.full((nf, W * H * 3 // 2), 0x55, dtype=torch.uint8, device=DEV)
+    _, d_px, d_dec = dec.decode_frames_device(torch.from_numpy(bs).to(DEV), torch.from_numpy(want["sizes"]).to(DEV), levels=False, d_frames=canvas)
+    torch.cuda.synchronize()
+    na = int(want["summary"][1])
+    pcm, status = xa_decode_streams(XaSettings(1 if s.format == 7 else 0, s.audio_channels == 2, 37800, 4), xa[:na].reshape(1, -1))
+    return want, d_px.cpu().numpy(), d_dec.cpu().numpy(), pcm[0], status[0]
+
+
 @pytest.mark.parametrize("fmt,channels", [(7, 2), (6, 1)])
 def test_whole_reader(fmt, channels):
-    import torch
-    from psxavenc_amd import MdecDecoder, strmux, xa_decode_streams
-    from psxavenc_amd.adpcm import XaSettings
+    from psxavenc_amd import MdecDecoder, strmux
     from psxavenc_amd.decode import DEC_EHEADER
     s, _, d_sectors, p, _ = clean_stream(fmt, 0, channels, 15, 20)
     sectors, nf = d_sectors.cpu().numpy(), p.n_frames_encoded
@@ -223,14 +237,7 @@ def test_whole_reader(fmt, channels):
     dec = MdecDecoder(W, H, dc_wrap=False, device=0)
 
     def expected(stream):
-        bs, xa = np.zeros((nf, stride), np.uint8), np.zeros((stream.shape[0], stream.shape[1]), np.uint8)
-        want = D.demux(s, stream, 1, nf, bs, xa)
-        canvas = torch.full((nf, W * H * 3 // 2), 0x55, dtype=torch.uint8, device=DEV)
-        _, d_px, d_dec = dec.decode_frames_device(torch.from_numpy(bs).to(DEV), torch.from_numpy(want["sizes"]).to(DEV), levels=False, d_frames=canvas)
-        torch.cuda.synchronize()
-        na = int(want["summary"][1])
-        pcm, status = xa_decode_streams(XaSettings(1 if fmt == 7 else 0, channels == 2, 37800, 4), xa[:na].reshape(1, -1))
-        return want, d_px.cpu().numpy(), d_dec.cpu().numpy(), pcm[0], status[0]
+        return _expected_read(s, dec, stream, nf, stride)
 
     reader = _reader()
     want, px, decoded, pcm, status = expected(sectors)
@@ -253,6 +260,28 @@ def test_whole_reader(fmt, channels):
     got3 = reader.read(s, sectors, nf, first_frame=-1, want_frames=False, pcm_sectors=2)
     assert got3["frames"] is None and np.array_equal(got3["decoded"], decoded) and np.array_equal(got3["pcm"], pcm[:got3["pcm"].size])
     assert got3["xa_status"].size == 2 and got3["summary"][7] == want["summary"][1] - 2
+    dec.close()
+
+
+def test_whole_reader_small_larger_small_on_one_handle():
+    """about 8, then about 64, then about 8 sectors of an STRCD stream with stereo 4-bit audio through read() of ONE fresh reader: its
+    workspace and staging buffers are allocated, outgrown and reused; every call against the same references as test_whole_reader"""
+    from psxavenc_amd import MdecDecoder, StrReader, strmux
+    s, _, d_sectors, p, _ = clean_stream(7, 0, 2, 15, 20)
+    sectors = d_sectors.cpu().numpy()
+    stride = int(strmux.frame_budgets(s, 0, p.n_frames_encoded).max())
+    assert sectors.shape[0] >= 64
+    dec = MdecDecoder(W, H, dc_wrap=False, device=0)
+    reader = StrReader(0)
+    for n, nf in ((8, 1), (64, 7), (9, 1)):
+        want, px, decoded, pcm, status = _expected_read(s, dec, sectors[:n], nf, stride)
+        got = reader.read(s, sectors[:n], nf, first_frame=1, frames=np.full((nf, W * H * 3 // 2), 0x55, np.uint8))
+        assert np.array_equal(got["info"], want["info"]) and np.array_equal(got["summary"], want["summary"]), n
+        assert np.array_equal(got["decoded"], decoded) and np.array_equal(got["frames"], px), n
+        assert got["pcm"].size == pcm.size > 0 and np.array_equal(got["pcm"], pcm), n
+        assert np.array_equal(got["xa_status"], status) and not status.any(), n
+        assert want["summary"][0] > 0 and (n < 64 or (decoded[:, 0] == 0).sum() >= 5), n      # video sectors; the long piece holds whole frames
+    reader.close()
     dec.close()
 
 
