@@ -1,6 +1,6 @@
 // adpcm_decode_kernels.hip -- the ADPCM way back for MI355X (gfx950), hand-written HIP: unit records -> int16 PCM
-// (adpcm_decode_kernel), the sums of squared errors of two sample sets per unit and per chain (adpcm_sse_kernel), XA sectors -> unit
-// records (xa_disassemble_kernel), and the device-level entry points of include/psxav_hip.h that launch them.  The arithmetic is
+// (adpcm_decode_kernel) and the sums of squared errors of two sample sets per unit and per chain (adpcm_sse_kernel); the entry points
+// of include/psxav_hip.h that launch them are psxhip_adpcm_decode.cpp, XA sectors -> unit records sector_kernels.hip.  The arithmetic is
 // "psxhip ADPCM decode v1" (adpcm_decode_core.h): the reconstruction inside the reference's encoder
 // (libpsxav/adpcm.c:120-124,135-136).
 //
@@ -17,17 +17,9 @@
 // over all banks instead of landing on a few.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
-
-#include <vector>
 
 #include "adpcm_decode_core.h"
-#include "device_buffer.h"
-#include "host_layout.h"
-#include "psxhip_internal.h"
-#include "xa_edc.h"
-
-#define PSXHIP_ADPCM_DECODE_KERNEL_REV "adpcm-dec-k1.0"
+#include "psxhip_adpcm_internal.h"
 
 namespace {
 
@@ -43,29 +35,6 @@ static_assert(kRound * 14 <= 64, "a work item's round is written by one store in
 __device__ __forceinline__ unsigned long long pack_state(int p1, int p2) {
     return (unsigned long long)(uint32_t)p1 | (unsigned long long)(uint32_t)p2 << 32;
 }
-
-struct DecodeJob {
-    const uint8_t* units;
-    const psxhip_adpcm_chain_t* chains;
-    const int32_t* unit_base;
-    int n_items;                         // work items: chains, or chunks when chunk_chain is given
-    int filter_count;
-    psxhip_adpcm_state_t* states;        // [n_chains] serial: read and updated; chunked: the start state of every chain's first chunk
-    int16_t* samples;
-    uint8_t* unit_flags;                 // optional: one byte per record index
-    int16_t* tail;                       // optional: 28 samples per chain, the unit sample_limit cuts
-    const int32_t* chunk_chain;          // [n_items] chain of each chunk; NULL: one work item per chain
-    const int32_t* chunk_first;          // [n_items] first unit (chain-local) of each chunk
-    const int32_t* chunk_pred;           // [n_items] the chunk in front of it in its chain (-1: the chain's first).  The two chains of an
-                                         //           interleaved stereo pair alternate chunk by chunk, so that L and R of the same stretch of
-                                         //           time are neighbouring lanes (see the write-out)
-    int chunk_units, warmup_units;
-    unsigned long long* start_used;      // [n_items] state each chunk was last decoded from (pack_state)
-    unsigned long long* chunk_end;       // [n_items] state behind each chunk's last unit -- kept here, not read back from PCM that
-                                         //           sample_limit may have kept from being stored
-    int* changed;                        // verify: set to 1 when any chunk was decoded again
-    const int* changed_before;           // verify: the previous pass's word (NULL: first pass of a batch); 0 there = nothing to do
-};
 
 template <int BITS>
 struct Geo {
@@ -110,7 +79,7 @@ __device__ __forceinline__ void stage_round(uint32_t* in_lds, int lane, const ui
 }
 
 template <bool VERIFY, int BITS>
-__global__ __launch_bounds__(64) void adpcm_decode_kernel(const DecodeJob job) {
+__global__ __launch_bounds__(64) void adpcm_decode_kernel(const psxhip_adpcm_decode_job_t job) {
     using G = Geo<BITS>;
     __shared__ __attribute__((aligned(16))) uint32_t in_lds[64 * G::kInRow];
     __shared__ __attribute__((aligned(16))) uint32_t out_lds[64 * G::kOutRow];
@@ -289,16 +258,6 @@ __global__ void adpcm_decode_final_kernel(const int32_t* last_chunk, const unsig
 }
 
 // ---- sums of squared errors: one lane per unit, one chain per blockIdx.x, blockIdx.y strides over the chain's units
-struct SseJob {
-    const int16_t* a;
-    const int16_t* b;
-    const int16_t* a_tail;               // optional: 28 samples per chain, what the decoder computed for the unit sample_limit cuts
-    const psxhip_adpcm_chain_t* chains;
-    const int32_t* unit_base;            // needed with unit_sse only
-    unsigned long long* unit_sse;        // optional: one sum per record index
-    unsigned long long* chain_sums;      // optional: [n_chains][2] = sum (a - b)^2, sum b^2 (zero before the launch)
-};
-
 __device__ __forceinline__ void sse_add(int av, int bv, unsigned long long& e, unsigned long long& bb) {
     const int d = av - bv;
     const uint32_t ad = (uint32_t)(d < 0 ? -d : d);           // <= 65535: the square fits 32 bits
@@ -330,7 +289,7 @@ __device__ __forceinline__ void sse_stage(const int16_t* chain0, long long first
     }
 }
 
-__global__ __launch_bounds__(64) void adpcm_sse_kernel(const SseJob job) {
+__global__ __launch_bounds__(64) void adpcm_sse_kernel(const psxhip_adpcm_sse_job_t job) {
     __shared__ uint32_t lds_a[kSseStageSamples / 2 + 1], lds_b[kSseStageSamples / 2 + 1];
     const int c = (int)blockIdx.x, lane = (int)(threadIdx.x & 63);
     const psxhip_adpcm_chain_t ch = job.chains[c];
@@ -383,338 +342,23 @@ __global__ __launch_bounds__(64) void adpcm_sse_kernel(const SseJob job) {
     }
 }
 
-// ---- XA sectors -> unit records in encode order: the inverse of xa_assemble_kernel (adpcm_kernels.hip), one workgroup per sector
-struct XaDisJob {
-    const uint8_t* sectors;
-    int n_sectors, format, stereo, frequency, bits;
-    uint8_t* units;
-    int32_t* status;        // optional
-    uint32_t eof_edc_delta; // EDC of an all-zero span with 0x80 at sector bytes 18 and 22
-};
-
-__global__ __launch_bounds__(256) void xa_disassemble_kernel(const XaDisJob job) {
-    __shared__ __attribute__((aligned(16))) uint8_t sec[2352];
-    __shared__ uint32_t crc_tab[256];
-    __shared__ int status;
-    const int tid = (int)threadIdx.x;
-    const int s = (int)blockIdx.x;
-    const bool four = job.bits == 4;
-    const int sector_size = job.format == 0 ? 2336 : 2352;
-    const int lead = 2352 - sector_size;
-    uint32_t* const sec32 = (uint32_t*)sec;
-
-    crc_tab[tid] = c_xa_tables[tid];
-    if (tid == 0) status = 0;
-    if (tid < lead / 4) sec32[tid] = 0u;
-    const uint32_t* src = (const uint32_t*)(job.sectors + (size_t)s * sector_size);
-    for (int i = tid; i < sector_size / 4; i += 256) sec32[lead / 4 + i] = src[i];
-    __syncthreads();
-
-    int bad = 0;
-    if (tid < 18) {
-        // a sound group's header copies: bytes 4..7 against 0..3, 12..15 against 8..11 (adpcm.c:212-219)
-        const uint32_t* grp = sec32 + (0x18 + tid * 128) / 4;
-        if (grp[0] != grp[1] || grp[2] != grp[3]) bad |= 1;
-    }
-    if (tid >= 64 && tid < 128) {
-        // one wavefront: subheaders, coding byte, the form-2 EDC over sector bytes 0x10 .. 0x92B (cdrom.c:102-110)
-        const int l = tid - 64;
-        const uint32_t sub0 = sec32[4], sub1 = sec32[5], stored = sec32[0x92C / 4];
-        if (l == 0) {
-            if (sub0 != sub1) bad |= 2;
-            const uint32_t coding = (uint32_t)((job.stereo ? 0x01 : 0) | (job.frequency == 37800 ? 0 : 0x04) | (four ? 0 : 0x10));
-            if ((sub0 >> 24) != coding) bad |= 4;
-        }
-        // psx_audio_xa_encode_finalize sets EOF in both subheaders behind the EDC and leaves the EDC as it was (adpcm.c:334-340):
-        // such a sector carries the EDC of the sector without the bits.  The CRC is linear over GF(2): that is this sector's EDC xor
-        // the EDC of a span that holds the two bits alone -- a constant (eof_edc_delta, from the host)
-        const uint32_t edc = (uint32_t)__shfl((int)edc_wave<kEdcSpan>(sec32, crc_tab, l), 0, 64);
-        const bool eof = (sub0 & sub1 & 0x00800000u) != 0u;
-        const bool ok = stored == 0u || stored == edc || (eof && stored == (edc ^ job.eof_edc_delta));
-        if (l == 0 && !ok) bad |= 8;
-    }
-    if (bad) atomicOr(&status, bad);
-
-    // 18 sound groups of 128 bytes at sector byte 0x18; 576 record dwords per sector either way
-    uint32_t* dst = (uint32_t*)job.units + (size_t)s * 576;
-    for (int i = tid; i < 576; i += 256) {
-        uint32_t v = 0;
-        if (four) {
-            // unit n of group g: header at group byte n (n < 4) or n + 4; sample w is nibble n & 1 of group byte 16 + 4 w + n / 2.  The
-            // record is an SPU block: [header][0][14 code bytes: sample 2 k low, 2 k + 1 high]
-            const int ui = i >> 2, q = i & 3, g = ui >> 3, n = ui & 7;
-            const uint8_t* grp = sec + 0x18 + g * 128;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int rb = 4 * q + k;
-                uint32_t byte = 0;
-                if (rb == 0) byte = grp[n + (n >= 4 ? 4 : 0)];
-                else if (rb >= 2) {
-                    const int w = 2 * (rb - 2), sh = 4 * (n & 1);
-                    byte = ((grp[16 + 4 * w + (n >> 1)] >> sh) & 15u) | (((grp[16 + 4 * (w + 1) + (n >> 1)] >> sh) & 15u) << 4);
-                }
-                v |= byte << (8 * k);
-            }
-        } else {
-            // unit n of group g: header at group byte n; sample w at group byte 16 + 4 w + n.  Record: [header][0][0][0][28 codes]
-            const int ui = i >> 3, q = i & 7, g = ui >> 2, n = ui & 3;
-            const uint8_t* grp = sec + 0x18 + g * 128;
-            if (q == 0) v = grp[n];
-            else {
-#pragma unroll
-                for (int k = 0; k < 4; k++) v |= (uint32_t)grp[16 + 4 * (4 * (q - 1) + k) + n] << (8 * k);
-            }
-        }
-        dst[i] = v;
-    }
-    __syncthreads();
-    if (tid == 0 && job.status) job.status[s] = status;
-}
-
-bool bad_coding(int filter_count, int bits) {
-    return (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || (bits == 8 && filter_count == 5);
-}
-
-template <bool VERIFY>
-void launch_decode(const DecodeJob& job, int bits, hipStream_t st) {
-    const dim3 grid((unsigned)((job.n_items + 63) / 64)), block(64);
-    if (bits == 4) hipLaunchKernelGGL((adpcm_decode_kernel<VERIFY, 4>), grid, block, 0, st, job);
-    else hipLaunchKernelGGL((adpcm_decode_kernel<VERIFY, 8>), grid, block, 0, st, job);
-}
-
 }  // namespace
 
-// measurement (psxhip_adpcm_decode_set_timing): the calling thread's switch and its last chunked call's two durations
-static thread_local bool g_timing = false;
-static thread_local float g_spec_ms = 0.f, g_verify_ms = 0.f;
-
-extern "C" int psxhip_adpcm_decode_set_timing(int on) {
-    g_timing = on != 0;
-    return PSXHIP_OK;
+extern "C" hipError_t psxhip_adpcm_decode_launch(const psxhip_adpcm_decode_job_t* j, int verify, int bits, void* stream) {
+    const auto kernel = verify ? (bits == 4 ? adpcm_decode_kernel<true, 4> : adpcm_decode_kernel<true, 8>)
+                               : (bits == 4 ? adpcm_decode_kernel<false, 4> : adpcm_decode_kernel<false, 8>);
+    void* args[] = {(void*)j};
+    return hipLaunchKernel((const void*)kernel, dim3((unsigned)((j->n_items + 63) / 64)), dim3(64), args, 0, (hipStream_t)stream);
 }
 
-extern "C" int psxhip_adpcm_decode_last_timing(float* speculate_ms, float* verify_ms) {
-    if (speculate_ms) *speculate_ms = g_spec_ms;
-    if (verify_ms) *verify_ms = g_verify_ms;
-    return PSXHIP_OK;
+extern "C" hipError_t psxhip_adpcm_decode_final_launch(const int32_t* last_chunk, const unsigned long long* chunk_end, int n_chains,
+                                                       psxhip_adpcm_state_t* states, void* stream) {
+    hipLaunchKernelGGL(adpcm_decode_final_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, (hipStream_t)stream, last_chunk,
+                       chunk_end, n_chains, states);
+    return hipGetLastError();
 }
 
-extern "C" const char* psxhip_adpcm_decode_kernel_rev(void) { return PSXHIP_ADPCM_DECODE_KERNEL_REV; }
-
-extern "C" int psxhip_adpcm_decode_chains_device(int device, const uint8_t* d_units, const psxhip_adpcm_chain_t* d_chains,
-                                                 const int32_t* d_unit_base, int n_chains, int filter_count, int bits,
-                                                 psxhip_adpcm_state_t* d_states, int16_t* d_samples, uint8_t* d_unit_flags, int16_t* d_tail,
-                                                 void* stream) {
-    if (n_chains < 0 || bad_coding(filter_count, bits) || (n_chains > 0 && (!d_units || !d_chains || !d_unit_base || !d_states || !d_samples)) ||
-        ((uintptr_t)d_units & 15) || ((uintptr_t)d_samples & 1) || ((uintptr_t)d_tail & 3)) {
-        psxhip_set_error("adpcm_decode_chains: bad argument (bits 4 or 8, filter_count 4 or 5 and 4 with 8 bits, d_units 16-byte aligned, d_tail 4-byte)");
-        return PSXHIP_EINVAL;
-    }
-    const int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (n_chains == 0) return PSXHIP_OK;
-    DecodeJob job;
-    memset(&job, 0, sizeof job);
-    job.units = d_units; job.chains = d_chains; job.unit_base = d_unit_base; job.n_items = n_chains; job.filter_count = filter_count;
-    job.states = d_states; job.samples = d_samples; job.unit_flags = d_unit_flags; job.tail = d_tail;
-    launch_decode<false>(job, bits, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
-    return PSXHIP_OK;
-}
-
-extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_units, const psxhip_adpcm_chain_t* chains,
-                                                  const int32_t* unit_base, int n_chains, int filter_count, int bits,
-                                                  psxhip_adpcm_state_t* d_states, int16_t* d_samples, uint8_t* d_unit_flags, int16_t* d_tail,
-                                                  int chunk_units, int warmup_units, int max_passes, void* stream) {
-    if (n_chains < 0 || bad_coding(filter_count, bits) || (n_chains > 0 && (!d_units || !chains || !unit_base || !d_states || !d_samples)) ||
-        ((uintptr_t)d_units & 15) || ((uintptr_t)d_samples & 1) || ((uintptr_t)d_tail & 3)) {
-        psxhip_set_error("adpcm_decode_chains_chunked: bad argument (bits 4 or 8, filter_count 4 or 5 and 4 with 8 bits, d_units 16-byte aligned, d_tail 4-byte)");
-        return PSXHIP_EINVAL;
-    }
-    long long total_units = 0;
-    for (int c = 0; c < n_chains; c++) {
-        if (chains[c].pitch < 1 || chains[c].n_units < 0) {
-            psxhip_set_error("adpcm_decode_chains_chunked: chain %d has pitch %d, n_units %d", c, chains[c].pitch, chains[c].n_units);
-            return PSXHIP_EINVAL;
-        }
-        total_units += chains[c].n_units;
-    }
-    const int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (total_units == 0) return 0;
-    HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
-    if (chunk_units <= 0) {
-        // the encoder's rule (pick_chunking) for wavefronts of 64 chunks: long chunks so that verify needs few passes, enough of them to
-        // fill the device.  A decode wavefront holds 64 chunks and a CU eight such wavefronts: at least four rounds of them
-        int w = 0, n_cu = 0;
-        psxhip_adpcm_pick_chunking(total_units, 64, device, &chunk_units, &w);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
-        const long long fill = total_units / (4ll * 8 * 64 * n_cu);
-        const long long want = fill < 256 ? 256 : fill;
-        if (want < chunk_units) chunk_units = (int)want;
-    }
-    if (warmup_units < 0) warmup_units = 64;       // decoding is cheap: a long warm-up, not the encoder's
-
-    // the chunk table: chain by chain, the two chains of an interleaved stereo pair chunk by chunk in turns
-    std::vector<int32_t> chunk_chain, chunk_first, chunk_pred, last_chunk((size_t)n_chains, -1);
-    for (int c = 0; c < n_chains;) {
-        const bool pair = c + 1 < n_chains && chains[c].pitch == 2 && chains[c + 1].pitch == 2 && chains[c].n_units > 0 &&
-                          chains[c + 1].sample_offset == chains[c].sample_offset + 1 && chains[c + 1].n_units == chains[c].n_units;
-        const int span = pair ? 2 : 1;
-        for (int f = 0; f < chains[c].n_units; f += chunk_units)
-            for (int k = 0; k < span; k++) {
-                const int32_t idx = (int32_t)chunk_chain.size();
-                last_chunk[c + k] = idx;
-                chunk_chain.push_back(c + k);
-                chunk_first.push_back(f);
-                chunk_pred.push_back(f ? idx - span : -1);
-            }
-        c += span;
-    }
-    const size_t n_chunks = chunk_chain.size();
-    if (n_chunks > 0x7FFFFFFFu) {
-        psxhip_set_error("adpcm_decode_chains_chunked: %zu chunks", n_chunks);
-        return PSXHIP_EINVAL;
-    }
-    constexpr int kBatchMax = 16;
-    BumpOffsets o;
-    const size_t o_chains = o.take(sizeof(psxhip_adpcm_chain_t) * n_chains), o_base = o.take(4 * (size_t)n_chains), o_cc = o.take(4 * n_chunks);
-    const size_t o_cf = o.take(4 * n_chunks), o_cp = o.take(4 * n_chunks), o_last = o.take(4 * (size_t)n_chains);
-    const size_t o_used = o.take(8 * n_chunks), o_end = o.take(8 * n_chunks), o_flags = o.take(sizeof(int) * kBatchMax);
-    DeviceBuffer ws;
-    const int rc_ws = ws.reserve(o.end);
-    if (rc_ws) return rc_ws;
-    uint8_t* const d = ws.as<uint8_t>();
-    hipStream_t st = (hipStream_t)stream;
-    // declared after the workspace: on every way out the stream has come to rest before the workspace goes, and the timing events go too
-    struct AtExit {
-        hipStream_t st;
-        bool at_rest;
-        hipEvent_t ev[3];
-        ~AtExit() {
-            if (!at_rest) (void)hipStreamSynchronize(st);
-            for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        }
-    } at_exit{st, false, {nullptr, nullptr, nullptr}};
-    hipEvent_t* const ev = at_exit.ev;
-    int passes = 0, result = PSXHIP_OK;
-    int h_flags[kBatchMax];
-    HIP_TRY(hipMemcpyAsync(d + o_chains, chains, sizeof(psxhip_adpcm_chain_t) * n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_base, unit_base, 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_cc, chunk_chain.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_cf, chunk_first.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_cp, chunk_pred.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_last, last_chunk.data(), 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    DecodeJob job;
-    memset(&job, 0, sizeof job);
-    job.units = d_units; job.chains = (const psxhip_adpcm_chain_t*)(d + o_chains); job.unit_base = (const int32_t*)(d + o_base);
-    job.n_items = (int)n_chunks; job.filter_count = filter_count; job.states = d_states; job.samples = d_samples;
-    job.unit_flags = d_unit_flags; job.tail = d_tail;
-    job.chunk_chain = (const int32_t*)(d + o_cc); job.chunk_first = (const int32_t*)(d + o_cf);
-    job.chunk_pred = (const int32_t*)(d + o_cp);
-    job.chunk_units = chunk_units; job.warmup_units = warmup_units;
-    job.start_used = (unsigned long long*)(d + o_used); job.chunk_end = (unsigned long long*)(d + o_end);
-    int* d_flags = (int*)(d + o_flags);
-    const bool timed = g_timing;
-    if (timed)
-        for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]), PSXHIP_EDEVICE);
-    if (timed) HIP_TRY(hipEventRecord(ev[0], st), PSXHIP_EDEVICE);
-    launch_decode<false>(job, bits, st);
-    HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
-    if (timed) HIP_TRY(hipEventRecord(ev[1], st), PSXHIP_EDEVICE);
-    // verify passes in batches, back to back; a pass looks at its predecessor's word and returns at once when that changed nothing
-    // (the encoder's scheme, psxhip_adpcm_session_run)
-    int batch = 3;
-    for (bool done = false; !done;) {
-        if (max_passes > 0 && passes + batch > max_passes) batch = max_passes - passes;
-        if (batch < 1) {
-            psxhip_set_error("adpcm_decode_chains_chunked: not converged after %d verify passes", passes);
-            result = PSXHIP_EINVAL;
-            break;
-        }
-        HIP_TRY(hipMemsetAsync(d_flags, 0, sizeof(int) * kBatchMax, st), PSXHIP_EDEVICE);
-        for (int i = 0; i < batch; i++) {
-            job.changed = d_flags + i;
-            job.changed_before = i ? d_flags + i - 1 : nullptr;
-            launch_decode<true>(job, bits, st);
-        }
-        HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
-        HIP_TRY(hipMemcpyAsync(h_flags, d_flags, sizeof(int) * (size_t)batch, hipMemcpyDeviceToHost, st), PSXHIP_EDEVICE);
-        HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
-        for (int i = 0; i < batch && !done; i++) {
-            passes++;
-            if (!h_flags[i]) done = true;
-        }
-        batch = batch * 2 < kBatchMax ? batch * 2 : kBatchMax;
-    }
-    if (result == PSXHIP_OK) {
-        hipLaunchKernelGGL(adpcm_decode_final_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, st,
-                           (const int32_t*)(d + o_last), (const unsigned long long*)(d + o_end), n_chains, d_states);
-        HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
-    }
-    if (timed) {
-        HIP_TRY(hipEventRecord(ev[2], st), PSXHIP_EDEVICE);
-        HIP_TRY(hipEventSynchronize(ev[2]), PSXHIP_EDEVICE);
-        HIP_TRY(hipEventElapsedTime(&g_spec_ms, ev[0], ev[1]), PSXHIP_EDEVICE);
-        HIP_TRY(hipEventElapsedTime(&g_verify_ms, ev[1], ev[2]), PSXHIP_EDEVICE);
-    }
-    HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
-    at_exit.at_rest = true;
-    return result == PSXHIP_OK ? passes : result;
-}
-
-extern "C" int psxhip_adpcm_sse_device(int device, const int16_t* d_a, const int16_t* d_a_tail, const int16_t* d_b,
-                                       const psxhip_adpcm_chain_t* d_chains, int n_chains, uint64_t* d_unit_sse, const int32_t* d_unit_base,
-                                       uint64_t* d_chain_sums, void* stream) {
-    if (n_chains < 0 || (n_chains > 0 && (!d_a || !d_b || !d_chains || (d_unit_sse && !d_unit_base))) || ((uintptr_t)d_a & 1) ||
-        ((uintptr_t)d_b & 1) || ((uintptr_t)d_a_tail & 1) || ((uintptr_t)d_unit_sse & 7) || ((uintptr_t)d_chain_sums & 7)) {
-        psxhip_set_error("adpcm_sse: NULL or misaligned argument, negative chain count, or d_unit_sse without d_unit_base");
-        return PSXHIP_EINVAL;
-    }
-    const int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (n_chains == 0) return PSXHIP_OK;
-    HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
-    if (d_chain_sums) HIP_TRY(hipMemsetAsync(d_chain_sums, 0, (size_t)n_chains * 2 * sizeof(uint64_t), (hipStream_t)stream), PSXHIP_EDEVICE);
-    SseJob job;
-    job.a = d_a; job.b = d_b; job.a_tail = d_a_tail; job.chains = d_chains; job.unit_base = d_unit_base;
-    job.unit_sse = (unsigned long long*)d_unit_sse; job.chain_sums = (unsigned long long*)d_chain_sums;
-    // the host does not know the chains' lengths: enough slices that a few long chains fill the device, few enough that many short
-    // chains do not launch mostly idle wavefronts
-    int slices = 16384 / n_chains;
-    slices = slices < 1 ? 1 : (slices > 1024 ? 1024 : slices);
-    hipLaunchKernelGGL(adpcm_sse_kernel, dim3((unsigned)n_chains, (unsigned)slices), dim3(64), 0, (hipStream_t)stream, job);
-    HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
-    return PSXHIP_OK;
-}
-
-extern "C" int psxhip_xa_disassemble_device(int device, const uint8_t* d_sectors, int n_sectors, int format, int stereo, int frequency,
-                                            int bits, uint8_t* d_units, int32_t* d_sector_status, void* stream) {
-    if (n_sectors < 0 || (format != 0 && format != 1) || (bits != 4 && bits != 8) || (n_sectors > 0 && (!d_sectors || !d_units)) ||
-        ((uintptr_t)d_sectors & 3) || ((uintptr_t)d_units & 3) || ((uintptr_t)d_sector_status & 3)) {
-        psxhip_set_error("xa_disassemble: bad argument (format 0 or 1, bits 4 or 8, pointers 4-byte aligned)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (n_sectors == 0) return PSXHIP_OK;
-    HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
-    if ((rc = xa_tables(device))) return rc;
-    XaDisJob job;
-    job.sectors = d_sectors; job.n_sectors = n_sectors; job.format = format; job.stereo = stereo; job.frequency = frequency; job.bits = bits;
-    job.units = d_units; job.status = d_sector_status;
-    static const uint32_t delta = [] {
-        uint32_t t[256], c = 0;
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t v = i;
-            for (int k = 0; k < 8; k++) v = (v >> 1) ^ ((v & 1u) ? 0xD8018001u : 0u);
-            t[i] = v;
-        }
-        for (int i = 0; i < kEdcSpan; i++) c = (c >> 8) ^ t[(c ^ ((i == 2 || i == 6) ? 0x80u : 0u)) & 0xFF];
-        return c;
-    }();
-    job.eof_edc_delta = delta;
-    hipLaunchKernelGGL(xa_disassemble_kernel, dim3((unsigned)n_sectors), dim3(256), 0, (hipStream_t)stream, job);
-    HIP_TRY(hipGetLastError(), PSXHIP_EDEVICE);
-    return PSXHIP_OK;
+extern "C" hipError_t psxhip_adpcm_sse_launch(const psxhip_adpcm_sse_job_t* j, int n_chains, int slices, void* stream) {
+    hipLaunchKernelGGL(adpcm_sse_kernel, dim3((unsigned)n_chains, (unsigned)slices), dim3(64), 0, (hipStream_t)stream, *j);
+    return hipGetLastError();
 }

@@ -1,8 +1,8 @@
 // adpcm_kernels.hip -- SPU / XA ADPCM filter x shift search for MI355X (gfx950), hand-written HIP.
 //
 // Replaces libpsxav/adpcm.c:39-191 (find_min_shift, attempt_to_encode, encode) for batches of
-// independent encoder chains, plus the SPU block packing (adpcm.c:367-372) and the XA sound-group /
-// sector assembly with its EDC (adpcm.c:193-233,266-332; cdrom.c:28-41,55-74,102-110).
+// independent encoder chains, plus the SPU block packing (adpcm.c:367-372).  (The XA sound-group / sector assembly that reads
+// the unit records is sector_kernels.hip; the C ABI over these kernels is psxhip_adpcm_encode.cpp.)
 //
 // A chain (one SPU stream, or one XA channel side) is serial in time: the two last DECODED samples
 // feed the next sound unit (adpcm.c:135-136).  Inside one unit the reference tries, for each of the
@@ -16,13 +16,8 @@
 //   * the winning lane stores the unit's record and its decoded state is broadcast to the row.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <string.h>
 
-#include <mutex>
-#include <vector>
-
-#include "psxhip_internal.h"
-#include "xa_edc.h"
+#include "psxhip_adpcm_internal.h"
 
 namespace {
 
@@ -51,17 +46,6 @@ __device__ __forceinline__ int wave_max(int v) {
     }
     return v;
 }
-
-struct ChainJob {
-    const int16_t* samples;
-    const psxhip_adpcm_chain_t* chains;
-    const int32_t* unit_base;
-    int n_chains;
-    int filter_count;   // 5 SPU, 4 XA
-    int range;          // 12 (4-bit) or 8 (8-bit)
-    psxhip_adpcm_state_t* states;
-    uint8_t* units;
-};
 
 // A wavefront's 64 lanes are cut into ROWS of candidates, one chain per row.  SPU has 5 filters x 3 shifts = 15 candidates:
 // 16-lane rows (= DPP rows), 4 chains per wavefront.  XA has 4 filters = 12 candidates: the time-parallel kernel packs
@@ -304,7 +288,7 @@ __device__ __forceinline__ void store_record(uint8_t* units, long long index, ui
     for (int w = 0; w < 7; w++) rec[1 + w] = pk_lds[w * 64 + lane];
 }
 
-__global__ __launch_bounds__(64, 8) void adpcm_chains_kernel(const ChainJob job) {
+__global__ __launch_bounds__(64, 8) void adpcm_chains_kernel(const psxhip_adpcm_chain_job_t job) {
     const int lane = (int)(threadIdx.x & 63);
     const int chain = (int)blockIdx.x * 4 + (lane >> 4);
     const bool chain_live = chain < job.n_chains;
@@ -353,23 +337,12 @@ __global__ __launch_bounds__(64, 8) void adpcm_chains_kernel(const ChainJob job)
 // memory, final states likewise.  One wavefront, up to four chains.  (The batched path's four H2D copies, two kernels, two D2H
 // copies and a synchronise cost 94 us per 28-sample call against ~3 us for the reference's own loop.)
 // ---------------------------------------------------------------------------------------------
-constexpr int kCallStageMax = 8192;      // int16 elements staged in LDS (an XA sector is 4032)
+constexpr int kCallStageMax = PSXHIP_ADPCM_CALL_STAGE_MAX;
 constexpr int kCallWarm = 8;             // units a speculating row runs from a zero state before its segment
 constexpr int kCallSpecMin = 24;         // chains shorter than this are encoded serially (nothing to win)
 constexpr int kCallHist = 96;            // longest speculated segment
-struct CallJob {
-    const int16_t* samples;                 // device-visible; chains' sample_offset counts from here
-    psxhip_adpcm_chain_t chains[4];
-    psxhip_adpcm_state_t states_in[4];
-    int32_t unit_base[4];
-    int n_chains, filter_count, range;
-    int stage_elems;                        // > 0: copy this many elements into LDS first (multiple of 8, <= kCallStageMax)
-    psxhip_adpcm_state_t* states_out;
-    uint8_t* units;                         // 32-byte records (XA), or NULL
-    uint8_t* spu_out;                       // packed 16-byte SPU blocks, or NULL
-};
 
-__global__ __launch_bounds__(64) void adpcm_call_kernel(const CallJob job) {
+__global__ __launch_bounds__(64) void adpcm_call_kernel(const psxhip_adpcm_call_job_t job) {
     const int lane = (int)(threadIdx.x & 63);
     const Candidate cd = make_candidate<16>(lane, job.filter_count, job.range);
     __shared__ __attribute__((aligned(16))) int16_t stage[kCallStageMax];
@@ -533,29 +506,9 @@ __global__ __launch_bounds__(64) void adpcm_call_kernel(const CallJob job) {
 // bit for bit, whatever the guesses were.  Worst case (states never coincide, e.g. pure tones) verify
 // advances one chunk per pass, which is the serial schedule.
 // ---------------------------------------------------------------------------------------------
-struct ChunkJob {
-    const int16_t* samples;
-    const psxhip_adpcm_chain_t* chains;
-    const int32_t* unit_base;        // record index of each chain's unit 0
-    const int64_t* state_base;       // index into unit_states of each chain's unit 0
-    const int32_t* chunk_chain;      // [n_chunks] chain of each chunk
-    const int32_t* chunk_first;      // [n_chunks] first unit (chain-local) of each chunk
-    int n_chunks, chunk_units, warmup_units;
-    int filter_count, range;
-    const psxhip_adpcm_state_t* chain_states;   // start state of every chain (the truth as far as it is known)
-    const int32_t* lead_units;                  // [n_chains] units available BEFORE the chain's first unit for guessing
-                                                //            its start state (0: start from chain_states as given)
-    const uint8_t* start_known;                 // [n_chains] 0: chain_states[c] is not known yet, keep the guess
-    psxhip_adpcm_state_t* unit_states;          // state after every unit
-    psxhip_adpcm_state_t* start_used;           // [n_chunks] state each chunk was last encoded from
-    uint8_t* units;
-    int* changed;                    // verify: set to 1 when any chunk had to be re-encoded (device memory, one word per pass)
-    const int* changed_before;       // verify: the previous pass's word, NULL for the first pass of a batch -- a pass whose
-                                     // predecessor changed nothing has nothing to do (the fixpoint was reached) and returns at once
-};
 
 template <bool VERIFY, int ROW>
-__global__ __launch_bounds__(64, VERIFY ? 4 : 8) void adpcm_chunks_kernel(const ChunkJob job) {
+__global__ __launch_bounds__(64, VERIFY ? 4 : 8) void adpcm_chunks_kernel(const psxhip_adpcm_chunk_job_t job) {
     constexpr int kRows = 64 / ROW;            // chains per wavefront: 4 or 5
     // Verify passes are launched several at a time, back to back, without a host round trip in between (a synchronise + launch
     // per pass was 40-50 us, as much as re-encoding 40 sound units); the passes after the one that changed nothing fall through here
@@ -697,272 +650,7 @@ __global__ void spu_pack_kernel(const uint8_t* units, int n_blocks, uint8_t* out
     *(uint4*)(out + (size_t)b * 16) = *(const uint4*)(units + (size_t)b * kRecordBytes4);
 }
 
-// ---- XA sector assembly.  One 256-thread workgroup per sector; the sector is built in LDS as a full
-// 2352-byte raw sector (the .xa form simply skips the first 16 bytes on write-out, adpcm.c:303-311).
-struct XaJob {
-    const uint8_t* units;
-    int n_sectors, format, stereo, frequency, bits, file_number, channel_number, first_lba;
-    const uint8_t* eof_flags;   // optional: eof_flags[s] != 0 sets the EOF submode bit (adpcm.c:334-340)
-    uint32_t eof_bits;          // ... or, without eof_flags, bit s for the first 32 sectors (the per-sector call: nothing to upload)
-    uint8_t* out;
-    // muxed streams (psxhip_str_encode_device): sector s goes to slot dst_sector[s] of the output -- its address (the header's time
-    // code, cdrom.c:61-65) is first_lba + that slot, like encode_file_str's sector counter (filefmt.c:450-503) -- and blockIdx.y
-    // walks independent streams with the same layout
-    const int32_t* dst_sector;  // optional [n_sectors]
-    size_t units_stream_stride; // bytes between the streams' unit records
-    size_t out_stream_stride;   // bytes between the streams' outputs
-};
-
-__device__ __forceinline__ uint8_t to_bcd(int v) { return (uint8_t)(v + (v / 10) * 6); }
-
-__global__ __launch_bounds__(256) void xa_assemble_kernel(const XaJob job) {
-    __shared__ __attribute__((aligned(16))) uint8_t sec[2352];
-    __shared__ uint32_t crc_tab[256];
-    const int tid = (int)threadIdx.x;
-    const int s = (int)blockIdx.x;
-    const bool four = job.bits == 4;
-    const int upg = four ? 8 : 4;                 // sound units per group
-    const int sector_size = job.format == 0 ? 2336 : 2352;
-    uint32_t* const sec32 = (uint32_t*)sec;
-
-    crc_tab[tid] = c_xa_tables[tid];
-    for (int i = tid; i < 2352 / 4; i += 256) sec32[i] = 0u;
-    __syncthreads();
-
-    if (tid == 255) {
-        if (job.format == 1) {       // psx_cdrom_init_sector, mode 2 (cdrom.c:55-74)
-            for (int i = 1; i <= 10; i++) sec[i] = 0xFF;
-            const int lba = job.first_lba + (job.dst_sector ? job.dst_sector[s] : s) + 150;
-            sec[12] = to_bcd(lba / 4500);
-            sec[13] = to_bcd((lba / 75) % 60);
-            sec[14] = to_bcd(lba % 75);
-            sec[15] = 0x02;
-        }
-        sec[16] = (uint8_t)job.file_number;
-        sec[17] = (uint8_t)(job.channel_number & 0x1F);
-        sec[18] = (uint8_t)(0x04 | 0x20 | 0x40);   // AUDIO | FORM2 | RT
-        sec[19] = (uint8_t)((job.stereo ? 0x01 : 0) | (job.frequency == 37800 ? 0 : 0x04) | (four ? 0 : 0x10));
-        sec[20] = sec[16]; sec[21] = sec[17]; sec[22] = sec[18]; sec[23] = sec[19];
-    }
-
-    // sound groups: 18 x 128 bytes at sector offset 0x18 (adpcm.c:193-233,311-322)
-    const uint8_t* rec0 = job.units + (size_t)blockIdx.y * job.units_stream_stride + (size_t)s * 18 * upg * (four ? kRecordBytes4 : kRecordBytes);
-    if (four) {
-        // 4-bit: sample w of the group's 8 units is the 4 bytes (u0 | u1 << 4, u2 | u3 << 4, u4 | u5 << 4, u6 | u7 << 4) at group
-        // byte 16 + 4 w.  A record is an SPU block: [header][0][14 code bytes, two samples each].  Thread (group, q) reads dword q
-        // of the 8 records -- code bytes 4 q - 2 .. 4 q + 1, i.e. samples 8 q - 4 .. 8 q + 3 (q = 0: its upper half only) -- pairs
-        // the low nibbles (even samples) and the high nibbles (odd samples) of unit pairs for four code bytes at once, and
-        // transposes 4 x 4 bytes twice: 32 contiguous sector bytes from 8 dword loads.
-        if (tid < 18 * 4) {
-            const int g = tid >> 2, q = tid & 3;
-            const uint32_t* gr = (const uint32_t*)(rec0 + (size_t)g * 8 * kRecordBytes4) + q;
-            uint32_t pe[4], po[4];
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const uint32_t lo = gr[(2 * c) * (kRecordBytes4 / 4)], hi = gr[(2 * c + 1) * (kRecordBytes4 / 4)];
-                pe[c] = (lo & 0x0F0F0F0Fu) | ((hi << 4) & 0xF0F0F0F0u);          // byte j: column c of the EVEN sample of code byte j
-                po[c] = ((lo >> 4) & 0x0F0F0F0Fu) | (hi & 0xF0F0F0F0u);          // ... of the ODD sample
-            }
-            // transpose: e[j] = (pe0.j, pe1.j, pe2.j, pe3.j) = the four bytes of sample 2 * (code byte j), o[j] likewise of the sample after it
-            uint32_t e[4], o[4];
-            {
-                const uint32_t a0 = __builtin_amdgcn_perm(pe[1], pe[0], 0x05010400u), a1 = __builtin_amdgcn_perm(pe[1], pe[0], 0x07030602u);
-                const uint32_t b0 = __builtin_amdgcn_perm(pe[3], pe[2], 0x05010400u), b1 = __builtin_amdgcn_perm(pe[3], pe[2], 0x07030602u);
-                e[0] = __builtin_amdgcn_perm(b0, a0, 0x05040100u); e[1] = __builtin_amdgcn_perm(b0, a0, 0x07060302u);
-                e[2] = __builtin_amdgcn_perm(b1, a1, 0x05040100u); e[3] = __builtin_amdgcn_perm(b1, a1, 0x07060302u);
-            }
-            {
-                const uint32_t a0 = __builtin_amdgcn_perm(po[1], po[0], 0x05010400u), a1 = __builtin_amdgcn_perm(po[1], po[0], 0x07030602u);
-                const uint32_t b0 = __builtin_amdgcn_perm(po[3], po[2], 0x05010400u), b1 = __builtin_amdgcn_perm(po[3], po[2], 0x07030602u);
-                o[0] = __builtin_amdgcn_perm(b0, a0, 0x05040100u); o[1] = __builtin_amdgcn_perm(b0, a0, 0x07060302u);
-                o[2] = __builtin_amdgcn_perm(b1, a1, 0x05040100u); o[3] = __builtin_amdgcn_perm(b1, a1, 0x07060302u);
-            }
-            // dword q holds record bytes 4 q .. 4 q + 3 = code bytes 4 q - 2 + j: samples 2 (4 q - 2 + j) and the one after
-            uint32_t* grp = sec32 + (0x18 + g * 128 + 16) / 4;        // the group's 28 sample dwords
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int cb = 4 * q - 2 + j;                         // code byte (q = 0: j = 0, 1 are header and flags)
-                if (cb >= 0) { grp[2 * cb] = e[j]; grp[2 * cb + 1] = o[j]; }
-            }
-        } else if (tid >= 128 && tid < 128 + 18 * 2) {
-            // header bytes: units {0,1,2,3} at 0..3 and 4..7, units {4..7} at 8..11 and 12..15
-            const int g = (tid - 128) >> 1, half = (tid - 128) & 1;
-            const uint8_t* gr = rec0 + (size_t)g * 8 * kRecordBytes4 + (size_t)half * 4 * kRecordBytes4;
-            const uint32_t h = (uint32_t)gr[0] | (uint32_t)gr[kRecordBytes4] << 8 | (uint32_t)gr[2 * kRecordBytes4] << 16 | (uint32_t)gr[3 * kRecordBytes4] << 24;
-            uint32_t* dst = sec32 + (0x18 + g * 128 + 8 * half) / 4;
-            dst[0] = h; dst[1] = h;
-        }
-    } else {
-        for (int i = tid; i < 18 * 128; i += 256) {
-            const int g = i >> 7, b = i & 127;
-            const uint8_t* gr = rec0 + (size_t)g * upg * kRecordBytes;
-            uint8_t v;
-            if (b < 16) {
-                // 8-bit: units 0..3 at 0..3 and 4..7, bytes 8..15 are never written by the reference (stay 0)
-                v = b < 8 ? gr[(b & 3) * kRecordBytes] : 0;
-            } else {
-                const int w = (b - 16) >> 2, col = (b - 16) & 3;          // sample index, byte column
-                v = gr[col * kRecordBytes + 4 + w];
-            }
-            sec[0x18 + i] = v;
-        }
-    }
-    __syncthreads();
-
-    // form-2 EDC over sector bytes 0x10 .. 0x92B (2332 bytes) -> 0x92C (cdrom.c:102-110): one wavefront (edc_wave).
-    // (Before round 4: 256 chunks of 10 bytes, every thread advancing its partial to the END of the span through up to eight
-    // bit-matrix products out of LDS -- four wavefronts x 8 products of 32 conditional xors where one wavefront x 6 does.)
-    if (tid < 64) {
-        const uint32_t c = edc_wave<kEdcSpan>(sec32, crc_tab, tid);
-        if (tid == 0) sec32[0x92C / 4] = c;
-        // psx_audio_xa_encode_finalize (adpcm.c:334-340) ORs EOF into both subheader copies AFTER the EDC was
-        // computed and does not refresh it; kept that way for byte parity.  (Same wavefront, behind its reads of the span.)
-        if (tid == 1 && (job.eof_flags ? job.eof_flags[s] != 0 : (s < 32 && ((job.eof_bits >> s) & 1u)))) {
-            sec[18] |= 0x80;
-            sec[22] = sec[18];
-        }
-    }
-    __syncthreads();
-
-    const int lead = 2352 - sector_size;
-    uint8_t* dst = job.out + (size_t)blockIdx.y * job.out_stream_stride + (size_t)(job.dst_sector ? job.dst_sector[s] : s) * sector_size;
-    for (int i = tid; i < sector_size / 4; i += 256) ((uint32_t*)dst)[i] = *(const uint32_t*)&sec[lead + 4 * i];
-}
-
-// ---- STR video sectors (psxhip_str_encode_device): what encode_file_str does around encode_sector_str for every video slot of the
-// stream (filefmt.c:462-475 with :73-91, mdec.c:782-832, cdrom.c:92-100) -- sector header and subheaders, the 32-byte chunk header,
-// 2016 bytes of the frame's bitstream, the form-1 EDC -- one workgroup per sector, the frames' bitstreams and results read where the
-// frame kernel left them in HBM.  tab[i] = {slot n in the stream, frame (-2: an audio slot with no samples left: a zero sector),
-// byte offset into the frame's bitstream, the frame's budget}.
-struct StrVideoJob {
-    const uint8_t* bs;                      // the frames' bitstreams, bs_stride apart, the streams' bs_stream_stride apart
-    size_t bs_stride, bs_stream_stride;
-    const psxhip_mdec_result_t* res;        // [streams][frames_per_stream]
-    int frames_per_stream;
-    const int4* tab;
-    int n_entries;
-    int format;                             // 6 STR, 7 STRCD, 9 STRV (format_t, args.h:45-58)
-    int sector_size;
-    int xa_file, xa_channel, video_id, width, height;
-    uint8_t* out;
-    size_t out_stream_stride;
-};
-
-__global__ __launch_bounds__(256) void str_video_sector_kernel(const StrVideoJob job) {
-    __shared__ __attribute__((aligned(16))) uint8_t sec[2352];
-    __shared__ uint32_t crc_tab[256];
-    const int tid = (int)threadIdx.x;
-    uint32_t* const sec32 = (uint32_t*)sec;
-    const int4 e = job.tab[blockIdx.x];
-    const int n = e.x, frame = e.y, offset = e.z, budget = e.w;
-    uint8_t* dst = job.out + (size_t)blockIdx.y * job.out_stream_stride + (size_t)n * (size_t)job.sector_size;
-    if (frame < 0) {        // an audio slot with no samples left: psx_audio_xa_encode writes nothing (adpcm.c:310); zero here
-        for (int i = tid; i < job.sector_size / 4; i += 256) ((uint32_t*)dst)[i] = 0u;
-        return;
-    }
-    crc_tab[tid] = c_xa_tables[tid];
-    for (int i = tid; i < 2352 / 4; i += 256) sec32[i] = 0u;
-    __syncthreads();
-    const int at = job.format == 6 ? 0x08 : (job.format == 7 ? 0x18 : 0x00);          // mdec.c:822-829
-    const uint8_t* fo = job.bs + (size_t)blockIdx.y * job.bs_stream_stride + (size_t)frame * job.bs_stride;
-    // the 2016 payload bytes: 504 dwords (the frame's bitstream and its slices are dword-aligned, and so is at + 0x20)
-    for (int i = tid; i < 2016 / 4; i += 256) sec32[(at + 0x20) / 4 + i] = ((const uint32_t*)(fo + offset))[i];
-    if (tid == 255) {
-        uint8_t* sub = nullptr;
-        if (job.format == 7) {               // psx_cdrom_init_sector(.., MODE2_FORM1), cdrom.c:55-74
-            for (int i = 1; i <= 10; i++) sec[i] = 0xFF;
-            const int lba = n + 150;
-            sec[12] = to_bcd(lba / 4500);
-            sec[13] = to_bcd((lba / 75) % 60);
-            sec[14] = to_bcd(lba % 75);
-            sec[15] = 0x02;
-            sub = sec + 16;
-        } else if (job.format == 6) {
-            sub = sec;
-        }
-        if (sub) {                           // init_sector_buffer_video, filefmt.c:73-91
-            sub[0] = (uint8_t)job.xa_file;
-            sub[1] = (uint8_t)(job.xa_channel & 0x1F);
-            sub[2] = (uint8_t)(0x08 | 0x40);     // DATA | RT
-            sub[3] = 0;
-            sub[4] = sub[0]; sub[5] = sub[1]; sub[6] = sub[2]; sub[7] = sub[3];
-        }
-        // the chunk header of encode_sector_str, mdec.c:782-820
-        uint8_t* hd = sec + at;
-        const unsigned bytes_used = (unsigned)job.res[(size_t)blockIdx.y * job.frames_per_stream + frame].bytes_used;
-        const unsigned fi = (unsigned)(frame + 1);          // frame_index counts from 1
-        hd[0x00] = 0x60; hd[0x01] = 0x01;
-        hd[0x02] = (uint8_t)job.video_id; hd[0x03] = (uint8_t)(job.video_id >> 8);
-        hd[0x04] = (uint8_t)(offset / 2016); hd[0x05] = (uint8_t)((offset / 2016) >> 8);
-        hd[0x06] = (uint8_t)(budget / 2016); hd[0x07] = (uint8_t)((budget / 2016) >> 8);
-        hd[0x08] = (uint8_t)fi; hd[0x09] = (uint8_t)(fi >> 8); hd[0x0A] = (uint8_t)(fi >> 16); hd[0x0B] = (uint8_t)(fi >> 24);
-        hd[0x0C] = (uint8_t)bytes_used; hd[0x0D] = (uint8_t)(bytes_used >> 8); hd[0x0E] = (uint8_t)(bytes_used >> 16); hd[0x0F] = (uint8_t)(bytes_used >> 24);
-        hd[0x10] = (uint8_t)job.width; hd[0x11] = (uint8_t)(job.width >> 8);
-        hd[0x12] = (uint8_t)job.height; hd[0x13] = (uint8_t)(job.height >> 8);
-        for (int i = 0; i < 8; i++) hd[0x14 + i] = fo[i];       // the BS header of the frame
-        hd[0x1C] = 0; hd[0x1D] = 0; hd[0x1E] = 0; hd[0x1F] = 0;
-    }
-    __syncthreads();
-    // psx_cdrom_calculate_checksums(.., MODE2_FORM1) as the reference's muxer calls it for every flavour (filefmt.c:474): the EDC of
-    // buffer bytes 0x10 .. 0x817 at 0x818 (the ECC behind it is not computed, cdrom.c:99)
-    if (tid < 64) {
-        const uint32_t c = edc_wave<kEdcSpanForm1>(sec32, crc_tab, tid);
-        if (tid == 0) sec32[0x818 / 4] = c;
-    }
-    __syncthreads();
-    for (int i = tid; i < job.sector_size / 4; i += 256) ((uint32_t*)dst)[i] = sec32[i];
-}
-
 }  // namespace
-
-extern "C" int psxhip_adpcm_encode_chains_device(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains,
-                                                 const int32_t* d_unit_base, int n_chains, int filter_count, int bits,
-                                                 psxhip_adpcm_state_t* d_states, uint8_t* d_units, void* stream) {
-    if (!d_samples || !d_chains || !d_unit_base || !d_states || !d_units || n_chains < 0 ||
-        (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || ((uintptr_t)d_units & 3)) {
-        psxhip_set_error("adpcm_encode_chains: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (n_chains == 0) return PSXHIP_OK;
-    ChainJob job;
-    job.samples = d_samples;
-    job.chains = d_chains;
-    job.unit_base = d_unit_base;
-    job.n_chains = n_chains;
-    job.filter_count = filter_count;
-    job.range = bits == 4 ? 12 : 8;
-    job.states = d_states;
-    job.units = d_units;
-    hipLaunchKernelGGL(adpcm_chains_kernel, dim3((unsigned)((n_chains + 3) / 4)), dim3(64), 0, (hipStream_t)stream, job);
-    if (hipGetLastError() != hipSuccess) {
-        psxhip_set_error("adpcm_encode_chains: launch failed");
-        return PSXHIP_EDEVICE;
-    }
-    return PSXHIP_OK;
-}
-
-extern "C" hipError_t psxhip_adpcm_call_launch(const psxhip_adpcm_call_t* a, void* stream) {
-    CallJob job;
-    memset(&job, 0, sizeof job);
-    job.samples = a->samples;
-    for (int c = 0; c < 4; c++) {
-        job.chains[c] = a->chains[c];
-        job.states_in[c] = a->states_in[c];
-        job.unit_base[c] = a->unit_base[c];
-    }
-    job.n_chains = a->n_chains;
-    job.filter_count = a->filter_count;
-    job.range = a->bits == 4 ? 12 : 8;
-    job.stage_elems = a->stage_elems;
-    job.states_out = a->states_out;
-    job.units = a->units;
-    job.spu_out = a->spu_out;
-    hipLaunchKernelGGL(adpcm_call_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, job);
-    return hipGetLastError();
-}
-extern "C" int psxhip_adpcm_call_stage_max(void) { return kCallStageMax; }
 
 // final state of every chain = state after its last unit
 __global__ void adpcm_gather_final_states_kernel(const psxhip_adpcm_chain_t* chains, const int64_t* state_base, int n_chains,
@@ -973,432 +661,34 @@ __global__ void adpcm_gather_final_states_kernel(const psxhip_adpcm_chain_t* cha
     if (n > 0) states[c] = unit_states[state_base[c] + n - 1];
 }
 
-namespace {
-// A session owns a dozen device buffers.  The one-call entry points (psxhip_adpcm_encode_chains_chunked and the *_host
-// wrappers above it) build and drop a session per call, and a dozen hipMalloc / hipFree pairs cost more than encoding a
-// minute of audio: freed blocks are parked per host thread and handed out again (smallest block that fits and is not more
-// than four times too large).  psxhip_release_scratch() empties the cache.  A session synchronises its stream before it
-// lets go of its buffers, so a parked block has no work in flight.
-struct BlockCache {
-    static constexpr int kMax = 32;
-    struct Entry { void* p; size_t cap; int device; };
-    Entry e[kMax];
-    int n = 0;
-    void* take(size_t need, int device, size_t* cap) {
-        int best = -1;
-        for (int i = 0; i < n; i++)
-            if (e[i].device == device && e[i].cap >= need && e[i].cap <= 4 * need + 4096 && (best < 0 || e[i].cap < e[best].cap)) best = i;
-        if (best < 0) return nullptr;
-        void* p = e[best].p;
-        *cap = e[best].cap;
-        e[best] = e[--n];
-        return p;
-    }
-    bool park(void* p, size_t cap, int device) {
-        if (n == kMax) return false;
-        e[n++] = Entry{p, cap, device};
-        return true;
-    }
-    void release() {
-        for (int i = 0; i < n; i++) (void)hipFree(e[i].p);
-        n = 0;
-    }
-    ~BlockCache() { release(); }
-};
-thread_local BlockCache g_blocks;
-
-struct DevMem {
-    void* p = nullptr;
-    size_t cap = 0;
-    int device = 0;
-    ~DevMem() {
-        if (p && !g_blocks.park(p, cap, device)) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t n) {
-        if (!n) n = 4;
-        (void)hipGetDevice(&device);
-        p = g_blocks.take(n, device, &cap);
-        if (p) return hipSuccess;
-        cap = (n + 255) & ~(size_t)255;
-        return hipMalloc(&p, cap);
-    }
-    template <typename T> T* as() { return (T*)p; }
-};
-}  // namespace
-
-extern "C" void psxhip_adpcm_release_blocks(void) { g_blocks.release(); }
-
-struct psxhip_adpcm_session {
-    int device, n_chains, n_chunks;
-    bool speculated;
-    hipStream_t stream;
-    ChunkJob job;
-    DevMem d_chains, d_base, d_sbase, d_cchain, d_cfirst, d_ustates, d_used, d_cstates, d_lead, d_final, d_known, d_flags;
-    int* h_flags = nullptr;     // page-locked: the verify passes' "changed" words travel back through it (a session's runs are serialised)
-    // optional (psxhip_adpcm_session_set_timing): HIP events around the speculate launch and the verify passes of a run
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool timing = false;
-    float spec_ms = 0.0f, verify_ms = 0.0f;
-    ~psxhip_adpcm_session() {
-        if (h_flags) (void)hipHostFree(h_flags);
-        for (int i = 0; i < 3; i++) if (ev[i]) (void)hipEventDestroy(ev[i]);
-    }
-};
-
-#define TRY(expr)                                                                                   \
-    do {                                                                                            \
-        hipError_t e__ = (expr);                                                                    \
-        if (e__ != hipSuccess) {                                                                    \
-            psxhip_set_error("%s failed: %s", #expr, hipGetErrorString(e__));                       \
-            return PSXHIP_EDEVICE;                                                                  \
-        }                                                                                           \
-    } while (0)
-
-extern "C" int psxhip_adpcm_session_create(psxhip_adpcm_session_t** out, int device, const int16_t* d_samples,
-                                           const psxhip_adpcm_chain_t* chains, const int32_t* unit_base,
-                                           const int32_t* lead_units, int n_chains, int filter_count, int bits,
-                                           uint8_t* d_units, int chunk_units, int warmup_units, void* stream) {
-    if (!out) return PSXHIP_EINVAL;
-    *out = nullptr;
-    if (!d_samples || !chains || !unit_base || !d_units || n_chains < 0 || (filter_count != 4 && filter_count != 5) ||
-        (bits != 4 && bits != 8) || chunk_units < 1 || warmup_units < 0 || ((uintptr_t)d_units & 3)) {
-        psxhip_set_error("adpcm_session_create: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    struct Guard {                       // frees the half-built session on every early return
-        psxhip_adpcm_session* p;
-        ~Guard() { delete p; }
-    } guard{new psxhip_adpcm_session()};
-    psxhip_adpcm_session* s = guard.p;
-    s->device = device;
-    s->n_chains = n_chains;
-    s->speculated = false;
-    s->stream = (hipStream_t)stream;
-
-    std::vector<int64_t> state_base((size_t)n_chains);
-    std::vector<int32_t> chunk_chain, chunk_first, lead((size_t)n_chains, 0);
-    int64_t total_units = 0;
-    for (int c = 0; c < n_chains; c++) {
-        state_base[(size_t)c] = total_units;
-        for (int f = 0; f < chains[c].n_units; f += chunk_units) {
-            chunk_chain.push_back(c);
-            chunk_first.push_back(f);
-        }
-        total_units += chains[c].n_units;
-        if (lead_units) lead[(size_t)c] = lead_units[c] < 0 ? 0 : lead_units[c];
-    }
-    s->n_chunks = (int)chunk_chain.size();
-    const int nc = n_chains ? n_chains : 1, nk = s->n_chunks ? s->n_chunks : 1;
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = s->d_chains.alloc(sizeof(psxhip_adpcm_chain_t) * nc);
-    if (e == hipSuccess) e = s->d_base.alloc(sizeof(int32_t) * nc);
-    if (e == hipSuccess) e = s->d_sbase.alloc(sizeof(int64_t) * nc);
-    if (e == hipSuccess) e = s->d_lead.alloc(sizeof(int32_t) * nc);
-    if (e == hipSuccess) e = s->d_cstates.alloc(sizeof(psxhip_adpcm_state_t) * nc);
-    if (e == hipSuccess) e = s->d_final.alloc(sizeof(psxhip_adpcm_state_t) * nc);
-    if (e == hipSuccess) e = s->d_known.alloc(nc);
-    if (e == hipSuccess) e = s->d_flags.alloc(64 * sizeof(int));
-    if (e == hipSuccess) e = s->d_cchain.alloc(sizeof(int32_t) * nk);
-    if (e == hipSuccess) e = s->d_cfirst.alloc(sizeof(int32_t) * nk);
-    if (e == hipSuccess) e = s->d_used.alloc(sizeof(psxhip_adpcm_state_t) * nk);
-    if (e == hipSuccess) e = s->d_ustates.alloc(sizeof(psxhip_adpcm_state_t) * (size_t)(total_units ? total_units : 1));
-    if (e != hipSuccess) {
-        psxhip_set_error("adpcm_session_create: hipMalloc failed: %s", hipGetErrorString(e));
-        return PSXHIP_ENOMEM;
-    }
-    hipStream_t st = s->stream;
-    if (n_chains) {
-        TRY(hipMemcpyAsync(s->d_chains.p, chains, sizeof(psxhip_adpcm_chain_t) * n_chains, hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(s->d_base.p, unit_base, sizeof(int32_t) * n_chains, hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(s->d_sbase.p, state_base.data(), sizeof(int64_t) * n_chains, hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(s->d_lead.p, lead.data(), sizeof(int32_t) * n_chains, hipMemcpyHostToDevice, st));
-    }
-    if (s->n_chunks) {
-        TRY(hipMemcpyAsync(s->d_cchain.p, chunk_chain.data(), sizeof(int32_t) * s->n_chunks, hipMemcpyHostToDevice, st));
-        TRY(hipMemcpyAsync(s->d_cfirst.p, chunk_first.data(), sizeof(int32_t) * s->n_chunks, hipMemcpyHostToDevice, st));
-    }
-    TRY(hipStreamSynchronize(st));    // the host vectors go out of scope
-
-    ChunkJob& job = s->job;
-    job.samples = d_samples;
-    job.chains = s->d_chains.as<psxhip_adpcm_chain_t>();
-    job.unit_base = s->d_base.as<int32_t>();
-    job.state_base = s->d_sbase.as<int64_t>();
-    job.chunk_chain = s->d_cchain.as<int32_t>();
-    job.chunk_first = s->d_cfirst.as<int32_t>();
-    job.n_chunks = s->n_chunks;
-    job.chunk_units = chunk_units;
-    job.warmup_units = warmup_units;
-    job.filter_count = filter_count;
-    job.range = bits == 4 ? 12 : 8;
-    job.chain_states = s->d_cstates.as<psxhip_adpcm_state_t>();
-    job.lead_units = s->d_lead.as<int32_t>();
-    job.start_known = s->d_known.as<uint8_t>();
-    job.unit_states = s->d_ustates.as<psxhip_adpcm_state_t>();
-    job.start_used = s->d_used.as<psxhip_adpcm_state_t>();
-    job.units = d_units;
-    job.changed = nullptr;      // set by session_run, per pass
-    job.changed_before = nullptr;
-    guard.p = nullptr;                   // ownership passes to the caller
-    *out = s;
-    return PSXHIP_OK;
+extern "C" hipError_t psxhip_adpcm_chains_launch(const psxhip_adpcm_chain_job_t* j, void* stream) {
+    hipLaunchKernelGGL(adpcm_chains_kernel, dim3((unsigned)((j->n_chains + 3) / 4)), dim3(64), 0, (hipStream_t)stream, *j);
+    return hipGetLastError();
 }
 
-// HIP events around the speculate launch and around the verify passes of every run that speculates (i.e. the first run after a
-// create / reset): bench.py's live kernel-level timing.  The events cost two extra packets per run; off by default.
-extern "C" int psxhip_adpcm_session_set_timing(psxhip_adpcm_session_t* s, int on) {
-    if (!s) return PSXHIP_EINVAL;
-    if (on && !s->ev[0]) {
-        if (hipSetDevice(s->device) != hipSuccess) return PSXHIP_EDEVICE;
-        for (int i = 0; i < 3; i++)
-            if (hipEventCreate(&s->ev[i]) != hipSuccess) { psxhip_set_error("adpcm_session_set_timing: hipEventCreate failed"); return PSXHIP_EDEVICE; }
-    }
-    s->timing = on != 0;
-    return PSXHIP_OK;
-}
-extern "C" int psxhip_adpcm_session_last_timing(const psxhip_adpcm_session_t* s, float* speculate_ms, float* verify_ms) {
-    if (!s) return PSXHIP_EINVAL;
-    if (speculate_ms) *speculate_ms = s->spec_ms;
-    if (verify_ms) *verify_ms = s->verify_ms;
-    return PSXHIP_OK;
-}
-extern "C" const char* psxhip_adpcm_kernel_rev(void) { return PSXHIP_ADPCM_KERNEL_REV; }
-
-extern "C" void psxhip_adpcm_session_reset(psxhip_adpcm_session_t* s) {
-    if (s) s->speculated = false;        // the next run speculates again from scratch (same buffers, same chunk tables)
+extern "C" hipError_t psxhip_adpcm_call_launch(const psxhip_adpcm_call_job_t* j, void* stream) {
+    hipLaunchKernelGGL(adpcm_call_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *j);
+    return hipGetLastError();
 }
 
-extern "C" void psxhip_adpcm_session_destroy(psxhip_adpcm_session_t* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    (void)hipStreamSynchronize(s->stream);
-    delete s;
+extern "C" hipError_t psxhip_adpcm_chunks_launch(const psxhip_adpcm_chunk_job_t* j, int verify, void* stream) {
+    // XA's 4 filters fill 12 of a row's lanes: 12-lane rows, five chunks per wavefront; SPU's 5 filters need 16-lane rows
+    const bool narrow = j->filter_count == 4;
+    const int per = narrow ? 5 : 4;
+    const auto kernel = verify ? (narrow ? adpcm_chunks_kernel<true, 12> : adpcm_chunks_kernel<true, 16>)
+                               : (narrow ? adpcm_chunks_kernel<false, 12> : adpcm_chunks_kernel<false, 16>);
+    void* args[] = {(void*)j};
+    return hipLaunchKernel((const void*)kernel, dim3((unsigned)((j->n_chunks + per - 1) / per)), dim3(64), args, 0, (hipStream_t)stream);
 }
 
-extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_adpcm_state_t* start_states,
-                                        const uint8_t* start_known, int max_passes, psxhip_adpcm_state_t* final_states,
-                                        int* any_change) {
-    if (!s || !start_states) {
-        psxhip_set_error("adpcm_session_run: NULL argument");
-        return PSXHIP_EINVAL;
-    }
-    if (any_change) *any_change = 0;
-    TRY(hipSetDevice(s->device));
-    hipStream_t st = s->stream;
-    if (s->n_chains == 0) return 0;
-    TRY(hipMemcpyAsync(s->d_cstates.p, start_states, sizeof(psxhip_adpcm_state_t) * s->n_chains, hipMemcpyHostToDevice, st));
-    if (start_known) TRY(hipMemcpyAsync(s->d_known.p, start_known, (size_t)s->n_chains, hipMemcpyHostToDevice, st));
-    else TRY(hipMemsetAsync(s->d_known.p, 1, (size_t)s->n_chains, st));
-    int passes = 0;
-    if (s->n_chunks) {
-        // "some chunk's start state changed" is one word of device memory per pass.  Passes are launched in batches, back to
-        // back: pass i + 1 looks at pass i's word when it starts and returns at once if nothing changed, so the host reads the
-        // words once per batch -- no synchronise + launch round trip (40-50 us) per pass.  The words travel back through a
-        // page-locked buffer of the session (a run is synchronous).
-        constexpr int kBatchMax = 64;          // (the flags' room; batches grow 3, 6, 12, 16, 16 ...)
-        int*& h_flags = s->h_flags;      // owned by the session (a buffer per calling thread leaked one per worker thread of the multi-device calls)
-        if (!h_flags && hipHostMalloc((void**)&h_flags, kBatchMax * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-            h_flags = nullptr;
-            psxhip_set_error("adpcm_session_run: no page-locked memory for the verify flags");
-            return PSXHIP_ENOMEM;
-        }
-        int* d_flags = s->d_flags.as<int>();
-        // XA's 4 filters fill 12 of a row's lanes: 12-lane rows, five chunks per wavefront; SPU's 5 filters need 16-lane rows
-        const bool narrow = s->job.filter_count == 4;
-        const int per = narrow ? 5 : 4;
-        const dim3 grid((unsigned)((s->n_chunks + per - 1) / per)), block(64);
-        const bool timed = s->timing && !s->speculated;
-        if (!s->speculated) {
-            s->job.changed = d_flags;
-            s->job.changed_before = nullptr;
-            if (timed) TRY(hipEventRecord(s->ev[0], st));
-            if (narrow) hipLaunchKernelGGL((adpcm_chunks_kernel<false, 12>), grid, block, 0, st, s->job);
-            else hipLaunchKernelGGL((adpcm_chunks_kernel<false, 16>), grid, block, 0, st, s->job);
-            TRY(hipGetLastError());
-            if (timed) TRY(hipEventRecord(s->ev[1], st));
-            s->speculated = true;
-            if (any_change) *any_change = 1;
-        }
-        // first batch: most material is done after "one pass that repairs + one that finds nothing"
-        // (measured, NOTEBOOK round 6: with every batch 48 passes a short stream's whole verify phase is ONE batch, no host round trip
-        //  in it -- the round trips cost nothing measurable)
-        int batch = 3;
-        for (bool done = false; !done;) {
-            if (max_passes > 0 && passes + batch > max_passes) batch = max_passes - passes;
-            if (batch < 1) {
-                psxhip_set_error("adpcm_session_run: not converged after %d verify passes", passes);
-                return PSXHIP_EINVAL;
-            }
-            TRY(hipMemsetAsync(d_flags, 0, kBatchMax * sizeof(int), st));
-            for (int i = 0; i < batch; i++) {
-                s->job.changed = d_flags + i;
-                s->job.changed_before = i ? d_flags + i - 1 : nullptr;
-                if (narrow) hipLaunchKernelGGL((adpcm_chunks_kernel<true, 12>), grid, block, 0, st, s->job);
-                else hipLaunchKernelGGL((adpcm_chunks_kernel<true, 16>), grid, block, 0, st, s->job);
-            }
-            TRY(hipGetLastError());
-            TRY(hipMemcpyAsync(h_flags, d_flags, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, st));
-            TRY(hipStreamSynchronize(st));
-            for (int i = 0; i < batch && !done; i++) {
-                passes++;                      // this pass ran
-                if (h_flags[i]) { if (any_change) *any_change = 1; }
-                else done = true;              // it changed nothing: the fixpoint; the passes behind it returned at once
-            }
-            batch = batch * 2 < 16 ? batch * 2 : 16;
-        }
-        if (timed) {
-            TRY(hipEventRecord(s->ev[2], st));
-            TRY(hipEventSynchronize(s->ev[2]));
-            TRY(hipEventElapsedTime(&s->spec_ms, s->ev[0], s->ev[1]));
-            TRY(hipEventElapsedTime(&s->verify_ms, s->ev[1], s->ev[2]));
-        }
-    }
-    // chains without units keep their start state
-    TRY(hipMemcpyAsync(s->d_final.p, s->d_cstates.p, sizeof(psxhip_adpcm_state_t) * s->n_chains, hipMemcpyDeviceToDevice, st));
-    hipLaunchKernelGGL(adpcm_gather_final_states_kernel, dim3((unsigned)((s->n_chains + 255) / 256)), dim3(256), 0, st,
-                       s->job.chains, s->job.state_base, s->n_chains, s->job.unit_states, s->d_final.as<psxhip_adpcm_state_t>());
-    TRY(hipGetLastError());
-    if (final_states)
-        TRY(hipMemcpyAsync(final_states, s->d_final.p, sizeof(psxhip_adpcm_state_t) * s->n_chains, hipMemcpyDeviceToHost, st));
-    TRY(hipStreamSynchronize(st));
-    return passes;
+extern "C" hipError_t psxhip_adpcm_final_states_launch(const psxhip_adpcm_chain_t* chains, const int64_t* state_base, int n_chains,
+                                                       const psxhip_adpcm_state_t* unit_states, psxhip_adpcm_state_t* states, void* stream) {
+    hipLaunchKernelGGL(adpcm_gather_final_states_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, (hipStream_t)stream, chains,
+                       state_base, n_chains, unit_states, states);
+    return hipGetLastError();
 }
 
-extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains,
-                                                  const int32_t* unit_base, int n_chains, int filter_count, int bits,
-                                                  psxhip_adpcm_state_t* d_states, uint8_t* d_units, int chunk_units,
-                                                  int warmup_units, int max_passes, void* stream) {
-    if (!d_states) {
-        psxhip_set_error("adpcm_encode_chains_chunked: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    if (n_chains == 0) return 0;
-    psxhip_adpcm_session_t* s = nullptr;
-    int rc = psxhip_adpcm_session_create(&s, device, d_samples, chains, unit_base, nullptr, n_chains, filter_count, bits, d_units,
-                                         chunk_units, warmup_units, stream);
-    if (rc) return rc;
-    std::vector<psxhip_adpcm_state_t> st((size_t)n_chains);
-    hipError_t e = hipMemcpy(st.data(), d_states, sizeof(psxhip_adpcm_state_t) * n_chains, hipMemcpyDeviceToHost);
-    int passes = PSXHIP_EDEVICE;
-    if (e == hipSuccess) {
-        passes = psxhip_adpcm_session_run(s, st.data(), nullptr, max_passes, st.data(), nullptr);
-        if (passes >= 0) e = hipMemcpy(d_states, st.data(), sizeof(psxhip_adpcm_state_t) * n_chains, hipMemcpyHostToDevice);
-    }
-    psxhip_adpcm_session_destroy(s);
-    if (e != hipSuccess) {
-        psxhip_set_error("adpcm_encode_chains_chunked: state copy failed: %s", hipGetErrorString(e));
-        return PSXHIP_EDEVICE;
-    }
-    return passes;
-}
-#undef TRY
-
-extern "C" int psxhip_spu_pack_device(int device, const uint8_t* d_units, int n_blocks, uint8_t* d_out, void* stream) {
-    if (!d_units || !d_out || n_blocks < 0 || ((uintptr_t)d_out & 15) || ((uintptr_t)d_units & 3)) {
-        psxhip_set_error("spu_pack: bad argument (d_out must be 16-byte aligned)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (n_blocks == 0) return PSXHIP_OK;
-    hipLaunchKernelGGL(spu_pack_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_units,
-                       n_blocks, d_out);
-    if (hipGetLastError() != hipSuccess) {
-        psxhip_set_error("spu_pack: launch failed");
-        return PSXHIP_EDEVICE;
-    }
-    return PSXHIP_OK;
-}
-
-extern "C" int psxhip_xa_assemble_device(int device, const uint8_t* d_units, int n_sectors, int format, int stereo,
-                                         int frequency, int bits, int file_number, int channel_number, int first_lba,
-                                         const uint8_t* d_eof_flags, uint8_t* d_out, void* stream) {
-    return psxhip_xa_assemble_device_bits(device, d_units, n_sectors, format, stereo, frequency, bits, file_number, channel_number, first_lba,
-                                          d_eof_flags, 0u, d_out, stream);
-}
-
-extern "C" int psxhip_xa_assemble_device_bits(int device, const uint8_t* d_units, int n_sectors, int format, int stereo,
-                                              int frequency, int bits, int file_number, int channel_number, int first_lba,
-                                              const uint8_t* d_eof_flags, uint32_t eof_bits, uint8_t* d_out, void* stream) {
-    return psxhip_xa_assemble_scatter(device, d_units, n_sectors, format, stereo, frequency, bits, file_number, channel_number, first_lba,
-                                      d_eof_flags, eof_bits, d_out, nullptr, 1, 0, 0, stream);
-}
-
-// ... n_streams streams of n_sectors sectors each (unit records units_stream_stride bytes apart, outputs out_stream_stride apart), every
-// sector s written to slot d_dst_sector[s] of its stream's output (NULL: slot s), its header address first_lba + that slot
-extern "C" int psxhip_xa_assemble_scatter(int device, const uint8_t* d_units, int n_sectors, int format, int stereo,
-                                          int frequency, int bits, int file_number, int channel_number, int first_lba,
-                                          const uint8_t* d_eof_flags, uint32_t eof_bits, uint8_t* d_out, const int32_t* d_dst_sector,
-                                          int n_streams, size_t units_stream_stride, size_t out_stream_stride, void* stream) {
-    if (!d_units || !d_out || n_sectors < 0 || n_streams < 1 || n_streams > 65535 || (format != 0 && format != 1) || (bits != 4 && bits != 8) ||
-        ((uintptr_t)d_out & 3) || (out_stream_stride & 3) || (units_stream_stride & 3)) {
-        psxhip_set_error("xa_assemble: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (n_sectors == 0) return PSXHIP_OK;
-    rc = xa_tables(device);
-    if (rc) return rc;
-    XaJob job;
-    job.units = d_units;
-    job.n_sectors = n_sectors;
-    job.format = format;
-    job.stereo = stereo;
-    job.frequency = frequency;
-    job.bits = bits;
-    job.file_number = file_number;
-    job.channel_number = channel_number;
-    job.first_lba = first_lba;
-    job.eof_flags = d_eof_flags;
-    job.eof_bits = eof_bits;
-    job.out = d_out;
-    job.dst_sector = d_dst_sector;
-    job.units_stream_stride = units_stream_stride;
-    job.out_stream_stride = out_stream_stride;
-    hipLaunchKernelGGL(xa_assemble_kernel, dim3((unsigned)n_sectors, (unsigned)n_streams), dim3(256), 0, (hipStream_t)stream, job);
-    if (hipGetLastError() != hipSuccess) {
-        psxhip_set_error("xa_assemble: launch failed");
-        return PSXHIP_EDEVICE;
-    }
-    return PSXHIP_OK;
-}
-
-
-extern "C" int psxhip_str_video_sectors_launch(int device, const psxhip_str_video_job_t* a, void* stream) {
-    if (!a || !a->d_bs || !a->d_res || !a->d_tab || !a->d_out || a->n_entries < 0 || a->n_streams < 1 || a->n_streams > 65535 ||
-        (a->bs_stride & 3) || (a->bs_stream_stride & 3) || (a->out_stream_stride & 3) || ((uintptr_t)a->d_bs & 3) || ((uintptr_t)a->d_out & 3)) {
-        psxhip_set_error("str_video_sectors: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
-    if (rc) return rc;
-    if (a->n_entries == 0) return PSXHIP_OK;
-    rc = xa_tables(device);
-    if (rc) return rc;
-    StrVideoJob job;
-    job.bs = a->d_bs;
-    job.bs_stride = a->bs_stride;
-    job.bs_stream_stride = a->bs_stream_stride;
-    job.res = a->d_res;
-    job.frames_per_stream = a->frames_per_stream;
-    job.tab = (const int4*)a->d_tab;
-    job.n_entries = a->n_entries;
-    job.format = a->format;
-    job.sector_size = a->sector_size;
-    job.xa_file = a->xa_file;
-    job.xa_channel = a->xa_channel;
-    job.video_id = a->video_id;
-    job.width = a->width;
-    job.height = a->height;
-    job.out = a->d_out;
-    job.out_stream_stride = a->out_stream_stride;
-    hipLaunchKernelGGL(str_video_sector_kernel, dim3((unsigned)a->n_entries, (unsigned)a->n_streams), dim3(256), 0, (hipStream_t)stream, job);
-    if (hipGetLastError() != hipSuccess) {
-        psxhip_set_error("str_video_sectors: launch failed");
-        return PSXHIP_EDEVICE;
-    }
-    return PSXHIP_OK;
+extern "C" hipError_t psxhip_spu_pack_launch(const uint8_t* units, int n_blocks, uint8_t* out, void* stream) {
+    hipLaunchKernelGGL(spu_pack_kernel, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, units, n_blocks, out);
+    return hipGetLastError();
 }

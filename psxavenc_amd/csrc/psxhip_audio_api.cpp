@@ -7,17 +7,19 @@
 #include <vector>
 
 #include "host_layout.h"
+#include "psxhip_adpcm_internal.h"
 #include "psxhip_internal.h"
 
 namespace {
 
 // streams at least this long are also split along time (psxhip_adpcm_encode_chains_chunked)
 constexpr int kChunkedThreshold = 4096;
+}  // namespace
 // ... and from 512 units when the call has only a few chains: one chain of 788 blocks (config `spu`'s second of audio) encoded serially
 // by one wavefront takes 1.35 ms, cut along time 0.98 ms; 2048 blocks 3.35 ms against 0.97 (the chunked path's set-up and verify round
 // trips are ~0.75 ms whatever the length, so below ~500 units serial wins; NOTEBOOK section 4).  Many short chains keep the
 // serial kernel: it runs them all side by side.
-inline int chunked_threshold(int n_chains) {
+extern "C" int psxhip_adpcm_chunked_threshold(int n_chains) {
     return n_chains <= 8 ? 512 : kChunkedThreshold;
 }
 
@@ -29,7 +31,7 @@ inline int chunked_threshold(int n_chains) {
 // SIMD with four wavefronts runs its VALU at 84 % and one with eight at ~100 %, and a launch of 3.7 wavefronts per SIMD ends
 // when the SIMDs that drew four do (config 5, 78 M units on one GPU: 1899 instead of 4096 units per chunk, 21.3 -> 24.4 M
 // sectors/s, still two verify passes; 1266: three passes, 950: four -- NOTEBOOK section 4).
-inline void pick_chunking(long long total_units, int rows, int device, int* chunk_units, int* warmup_units) {
+extern "C" void psxhip_adpcm_pick_chunking(long long total_units, int rows, int device, int* chunk_units, int* warmup_units) {
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
     const long long per_round = 32ll * n_cu * rows;                        // chunks in flight when every slot holds a wavefront
@@ -47,11 +49,6 @@ inline void pick_chunking(long long total_units, int rows, int device, int* chun
     *warmup_units = p >= 1024 ? 32 : 16;     // noisy material converges within a few units, tonal material not within 1024 either
 }
 
-}  // namespace
-extern "C" int psxhip_adpcm_chunked_threshold(int n_chains) { return chunked_threshold(n_chains); }
-extern "C" void psxhip_adpcm_pick_chunking(long long total_units, int rows, int device, int* chunk_units, int* warmup_units) {
-    pick_chunking(total_units, rows, device, chunk_units, warmup_units);
-}
 namespace {
 
 // Device scratch of the host-buffer entry points.  The reference calls psx_audio_spu_encode once per 28 samples and
@@ -180,9 +177,9 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
     if (rc) return rc;
 
     // ---- the reference's call pattern (a few streams, a few blocks): one launch, no copies (see CallScratch)
-    if (n_streams <= 4 && n_units < chunked_threshold(n_streams) && (size_t)n_streams * ((size_t)n_units * 28 + 8) <= (size_t)psxhip_adpcm_call_stage_max() &&
+    if (n_streams <= 4 && n_units < psxhip_adpcm_chunked_threshold(n_streams) && (size_t)n_streams * ((size_t)n_units * 28 + 8) <= (size_t)PSXHIP_ADPCM_CALL_STAGE_MAX &&
         (size_t)n_streams * bytes <= CallScratch::kOut && g_call.ready(device)) {
-        psxhip_adpcm_call_t a;
+        psxhip_adpcm_call_job_t a;
         memset(&a, 0, sizeof a);
         const size_t row = ((size_t)n_units * 28 + 7) & ~(size_t)7;      // staged row per stream: pitch 1, zero-padded to whole units
         int16_t* in = g_call.in();
@@ -199,7 +196,7 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
         a.stage_elems = (int)(row * n_streams);
         a.n_chains = n_streams;
         a.filter_count = 5;
-        a.bits = 4;
+        a.range = 12;
         a.states_out = g_call.d_states();
         a.spu_out = g_call.d_out();
         HIP_TRY(psxhip_adpcm_call_launch(&a, g_call.stream), PSXHIP_EDEVICE);
@@ -234,11 +231,11 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
     HIP_TRY(hipMemcpyAsync(d_c.p, chains.data(), chains.size() * sizeof(chains[0]), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_b.p, base.data(), base.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_st.p, states, n_streams * sizeof(psxhip_adpcm_state_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    if (n_units >= chunked_threshold(n_streams)) {
+    if (n_units >= psxhip_adpcm_chunked_threshold(n_streams)) {
         // long streams: parallel along time as well (speculate-and-verify; same bytes as the serial chain kernel)
         HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
         int chunk_units, warmup_units;
-        pick_chunking((long long)n_units * n_streams, 4, device, &chunk_units, &warmup_units);
+        psxhip_adpcm_pick_chunking((long long)n_units * n_streams, 4, device, &chunk_units, &warmup_units);
         rc = psxhip_adpcm_encode_chains_chunked(device, d_s.as<int16_t>(), chains.data(), base.data(), n_streams, 5, 4,
                                                 d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), chunk_units, warmup_units, 0, st);
         if (rc < 0) return rc;
@@ -298,12 +295,12 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
     if (n_streams == 1) stream_stride = (int64_t)per;             // a single stream needs no stride
     // ---- the reference's call pattern (one stream, a sector or two per call, filefmt.c:184,476-491): chains + assembly, two
     //      launches, no copies (see CallScratch)
-    if (n_streams == 1 && sectors <= 6 && ((per + 7) & ~(size_t)7) <= (size_t)psxhip_adpcm_call_stage_max() && (size_t)bytes <= CallScratch::kOut &&
+    if (n_streams == 1 && sectors <= 6 && ((per + 7) & ~(size_t)7) <= (size_t)PSXHIP_ADPCM_CALL_STAGE_MAX && (size_t)bytes <= CallScratch::kOut &&
         g_call.ready(device)) {
         g_pool_device = device;
         DevBuf d_u(4);
         HIP_TRY(d_u.alloc((size_t)units_per_stream * PSXHIP_ADPCM_RECORD_BYTES), PSXHIP_ENOMEM);
-        psxhip_adpcm_call_t a;
+        psxhip_adpcm_call_job_t a;
         memset(&a, 0, sizeof a);
         const size_t row = (per + 7) & ~(size_t)7;
         memcpy(g_call.in(), samples, per * sizeof(int16_t));
@@ -314,15 +311,15 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
         a.stage_elems = (int)row;
         a.n_chains = ch;
         a.filter_count = 4;
-        a.bits = bits;
+        a.range = bits == 4 ? 12 : 8;
         a.states_out = g_call.d_states();
         a.units = d_u.as<uint8_t>();
         uint32_t eof_bits = 0;
         for (int k = 0; k < sectors; k++)
             if (eof_flags ? eof_flags[k] != 0 : (finalize && k == sectors - 1)) eof_bits |= 1u << k;
         HIP_TRY(psxhip_adpcm_call_launch(&a, g_call.stream), PSXHIP_EDEVICE);
-        rc = psxhip_xa_assemble_device_bits(device, d_u.as<uint8_t>(), sectors, format, stereo, frequency, bits, file_number, channel_number,
-                                            lbas ? lbas[0] : 0, nullptr, eof_bits, g_call.d_out(), g_call.stream);
+        rc = psxhip_xa_assemble_scatter(device, d_u.as<uint8_t>(), sectors, format, stereo, frequency, bits, file_number, channel_number,
+                                        lbas ? lbas[0] : 0, nullptr, eof_bits, g_call.d_out(), nullptr, 1, 0, 0, g_call.stream);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(g_call.stream), PSXHIP_EDEVICE);
         memcpy(out, g_call.out(), (size_t)bytes);
@@ -355,10 +352,10 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
     HIP_TRY(hipMemcpyAsync(d_b.p, base.data(), base.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_st.p, states, chains.size() * sizeof(psxhip_adpcm_state_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_e.p, eof.data(), eof.size(), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    if (units_per_chain >= chunked_threshold((int)chains.size())) {
+    if (units_per_chain >= psxhip_adpcm_chunked_threshold((int)chains.size())) {
         HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
         int chunk_units, warmup_units;
-        pick_chunking((long long)units_per_chain * (long long)chains.size(), 5, device, &chunk_units, &warmup_units);
+        psxhip_adpcm_pick_chunking((long long)units_per_chain * (long long)chains.size(), 5, device, &chunk_units, &warmup_units);
         rc = psxhip_adpcm_encode_chains_chunked(device, d_s.as<int16_t>(), chains.data(), base.data(), (int)chains.size(), 4, bits,
                                                 d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), chunk_units, warmup_units, 0, st);
         if (rc < 0) return rc;

@@ -91,43 +91,11 @@ int psxhip_xa_encode_streams_host_flags(int device, int format, int stereo, int 
                                         int samples_per_stream, const int32_t *lbas, psxhip_adpcm_state_t *states,
                                         uint8_t *out, int64_t out_stride, int finalize, const uint8_t *eof_flags);
 
-/* one launch for the reference's per-call pattern (adpcm_call_kernel): up to four chains, descriptors and start states in the
- * kernel arguments, samples read from device-visible (page-locked host) memory */
-typedef struct {
-	const int16_t *samples;
-	int stage_elems;                     /* > 0: elements (multiple of 8, <= psxhip_adpcm_call_stage_max()) staged in LDS first */
-	psxhip_adpcm_chain_t chains[4];
-	psxhip_adpcm_state_t states_in[4];
-	int32_t unit_base[4];
-	int n_chains, filter_count, bits;
-	psxhip_adpcm_state_t *states_out;    /* [n_chains] */
-	uint8_t *units;                      /* unit records (PSXHIP_ADPCM_RECORD_SIZE(bits) apart), or NULL when spu_out is given */
-	uint8_t *spu_out;                    /* packed 16-byte SPU blocks */
-} psxhip_adpcm_call_t;
-hipError_t psxhip_adpcm_call_launch(const psxhip_adpcm_call_t *a, void *stream);
-int psxhip_adpcm_call_stage_max(void);
-int psxhip_xa_assemble_device_bits(int device, const uint8_t *d_units, int n_sectors, int format, int stereo, int frequency, int bits,
-                                   int file_number, int channel_number, int first_lba, const uint8_t *d_eof_flags, uint32_t eof_bits,
-                                   uint8_t *d_out, void *stream);
-
+/* n_streams streams of n_sectors sectors each; eof_bits: without d_eof_flags, bit s = EOF for the first 32 sectors */
 int psxhip_xa_assemble_scatter(int device, const uint8_t *d_units, int n_sectors, int format, int stereo, int frequency, int bits,
                                int file_number, int channel_number, int first_lba, const uint8_t *d_eof_flags, uint32_t eof_bits,
                                uint8_t *d_out, const int32_t *d_dst_sector, int n_streams, size_t units_stream_stride,
                                size_t out_stream_stride, void *stream);
-/* video sectors of muxed STR streams, built on the device (adpcm_kernels.hip: str_video_sector_kernel) */
-typedef struct {
-	const uint8_t *d_bs;                 /* the frames' bitstreams */
-	size_t bs_stride, bs_stream_stride;
-	const psxhip_mdec_result_t *d_res;   /* [n_streams][frames_per_stream] */
-	int frames_per_stream;
-	const int32_t *d_tab;                /* [n_entries][4]: slot in the stream, frame (-2: zero sector), byte offset into the bitstream, the frame's budget */
-	int n_entries, n_streams;
-	int format, sector_size;
-	int xa_file, xa_channel, video_id, width, height;
-	uint8_t *d_out;
-	size_t out_stream_stride;
-} psxhip_str_video_job_t;
-int psxhip_str_video_sectors_launch(int device, const psxhip_str_video_job_t *a, void *stream);
 void psxhip_adpcm_pick_chunking(long long total_units, int rows, int device, int *chunk_units, int *warmup_units);
 /* units per chain from which a chain is cut along time (speculate-and-verify) instead of run serially; the host entry points and
  * psxhip_str_encode_device ask the same function */
@@ -158,6 +126,36 @@ typedef struct {
 size_t psxhip_afe_lds_bytes(const psxhip_afe_job_t *j);
 hipError_t psxhip_afe_prepare(int dch, int coef_lds, size_t lds_bytes);
 hipError_t psxhip_afe_launch(const psxhip_afe_job_t *j, int grid, void *stream);
+
+/* the scaler (frontend_kernels.hip; C ABI: psxhip_scaler.cpp) */
+typedef struct {              /* one separable filter bank on the device */
+	const int32_t *left;      /* [n] */
+	const int16_t *coef;      /* [n * taps] */
+	const uint32_t *digits;   /* [n * 2 * taps4] horizontal banks: the taps as two balanced int8 digits (c = 256 h + l), four taps
+	                           *                 to a dword, zero-padded to taps4 dwords: first the l dwords, then the h dwords */
+	int taps, taps4;
+} psxhip_scaler_bank_t;
+
+typedef struct {
+	const uint8_t *src;
+	size_t src_stride;
+	uint8_t *out;
+	size_t frame_stride;
+	int sw, sh, dw, dh;
+	int limited;              /* YUV input in MPEG range: expand on the intermediates */
+	psxhip_scaler_bank_t lh, lv, ch, cv;      /* luma / chroma, horizontal / vertical */
+	int csw, csh;             /* chroma source plane size (sw/2 x sh/2 for YUV420P, sw x sh for RGB) */
+	int TW, TH;               /* luma tile; the chroma tile is TW/2 x TH/2 */
+	int tiles_x, tiles_y;
+	int vsegs;                /* vertical segments per band (blockIdx.z): each re-reads the rows its first tile reaches */
+	int reg_rows, reg_cols;   /* LDS region capacity per plane (RGB: the union of the luma and chroma reach; YUV: luma) */
+	int creg_rows, creg_cols; /* ... of a chroma plane (YUV) */
+} psxhip_scaler_job_t;
+
+/* lets the kernel of this source format (yuv: YUV420P, else RGB24) take up to max_lds bytes of dynamic LDS */
+hipError_t psxhip_scaler_prepare(int yuv, int max_lds);
+/* n_frames (<= 65535) frames from j->src on: grid = tiles_x bands x n_frames x vsegs */
+hipError_t psxhip_scaler_launch(const psxhip_scaler_job_t *j, int yuv, int n_frames, size_t lds_bytes, void *stream);
 
 void psxhip_set_error(const char *fmt, ...);
 

@@ -25,6 +25,7 @@
 #include "../../include/psxav_mdec.h"
 #include "device_buffer.h"
 #include "host_layout.h"
+#include "psxhip_adpcm_internal.h"
 #include "psxhip_internal.h"
 
 namespace {
@@ -616,6 +617,30 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     // ---- video: one batched launch over the frames of all streams, then the sector kernel, both on the caller's stream
     psxhip_str_video_job_t vj;
     memset(&vj, 0, sizeof vj);
+    vj.bs = d.buf.bs.as<const uint8_t>();
+    vj.bs_stride = ostride;
+    vj.bs_stream_stride = ostride * (size_t)nf;
+    vj.res = d.buf.res.as<const psxhip_mdec_result_t>();
+    vj.frames_per_stream = nf;
+    vj.tab = d.buf.vtab.as<const int4>();
+    vj.n_entries = d.n_vtab;
+    vj.format = s->format;
+    vj.sector_size = (int)ssz;
+    vj.xa_file = s->audio_xa_file;
+    vj.xa_channel = s->audio_xa_channel;
+    vj.video_id = s->str_video_id;
+    vj.width = s->video_width;
+    vj.height = s->video_height;
+    vj.out = d_out;
+    vj.out_stream_stride = out_stream_stride;
+    // (d_out, n_streams and the strides -- what comes from outside the library -- were checked above; the rest is this handle's own)
+    auto video_sectors = [&]() -> int {
+        if (vj.n_entries == 0) return PSXHIP_OK;
+        const int rc = psxhip_sector_tables(device);
+        if (rc) return rc;
+        HIP_TRY(psxhip_str_video_sectors_launch(&vj, n_streams, S), PSXHIP_EDEVICE);
+        return PSXHIP_OK;
+    };
     if (nf) {
         const int key[4] = {s->video_codec, s->video_width, s->video_height, pl.pub.max_frame_size};
         if (!d.mdec || memcmp(key, d.mdec_key, sizeof key) != 0) {
@@ -636,36 +661,12 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             b.d_results = d.buf.res.as<psxhip_mdec_result_t>() + (size_t)i * nf;
             batches.push_back(b);
         }
-        int rc = psxhip_mdec_encode_batches_device(d.mdec, batches.data(), (int)batches.size(), fsz, 0, ostride, S);
-        if (rc) return rc;
-        vj.d_bs = d.buf.bs.as<const uint8_t>();
-        vj.bs_stride = ostride;
-        vj.bs_stream_stride = ostride * (size_t)nf;
-        vj.d_res = d.buf.res.as<const psxhip_mdec_result_t>();
-        vj.frames_per_stream = nf;
-        vj.d_tab = d.buf.vtab.as<const int32_t>();
-        vj.n_entries = d.n_vtab;
-        vj.n_streams = n_streams;
-        vj.format = s->format;
-        vj.sector_size = (int)ssz;
-        vj.xa_file = s->audio_xa_file;
-        vj.xa_channel = s->audio_xa_channel;
-        vj.video_id = s->str_video_id;
-        vj.width = s->video_width;
-        vj.height = s->video_height;
-        vj.d_out = d_out;
-        vj.out_stream_stride = out_stream_stride;
-        rc = psxhip_str_video_sectors_launch(device, &vj, S);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(d.h_res, d.buf.res.p, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
-    } else if (d.n_vtab) {
-        // no frame in the stream, but audio slots without samples: zero sectors (nothing reads a bitstream)
-        vj.d_bs = d.buf.bs.as<const uint8_t>(); vj.d_res = d.buf.res.as<const psxhip_mdec_result_t>(); vj.d_tab = d.buf.vtab.as<const int32_t>();
-        vj.n_entries = d.n_vtab; vj.n_streams = n_streams; vj.format = s->format; vj.sector_size = (int)ssz; vj.d_out = d_out;
-        vj.out_stream_stride = out_stream_stride;
-        const int rc = psxhip_str_video_sectors_launch(device, &vj, S);
+        const int rc = psxhip_mdec_encode_batches_device(d.mdec, batches.data(), (int)batches.size(), fsz, 0, ostride, S);
         if (rc) return rc;
     }
+    // (no frame in the stream, but audio slots without samples: zero sectors -- nothing reads a bitstream)
+    if (const int rc = video_sectors()) return rc;
+    if (nf) HIP_TRY(hipMemcpyAsync(d.h_res, d.buf.res.p, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
 
     // ---- audio: the streams' XA tracks as chains of one session on the handle's own stream, behind the caller's inputs; the
     //      host drives the verify passes (the call is synchronous), the video leg above runs meanwhile
@@ -752,7 +753,7 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         if (!again.empty()) {
             int rc = psxhip_mdec_encode_batches_frame_kernel(d.mdec, again.data(), (int)again.size(), fsz, 0, ostride, S);
             if (rc) return rc;
-            rc = psxhip_str_video_sectors_launch(device, &vj, S);
+            rc = video_sectors();
             if (rc) return rc;
             HIP_TRY(hipMemcpyAsync(d.h_res, d.buf.res.p, sizeof(psxhip_mdec_result_t) * (size_t)nf * n_streams, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
             HIP_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);

@@ -1,5 +1,5 @@
 // xa_edc.h -- the EDC (CRC-32, polynomial 0xD8018001) of a CD-ROM XA sector by one wavefront, and the tables it needs.  Shared by the
-// sector assembly (adpcm_kernels.hip) and its inverse (adpcm_decode_kernels.hip); every translation unit that includes it owns a
+// sector kernels (sector_kernels.hip) and the STR reader (str_demux_kernels.hip); every translation unit that includes it owns a
 // copy of the tables and uploads it with its own xa_tables().
 #pragma once
 #include <hip/hip_runtime.h>

@@ -270,6 +270,60 @@ def test_chunked_long_chain_property():
             assert d_states.cpu().numpy()[0].tolist() == [st.prev1, st.prev2]
 
 
+def test_exhausted_max_passes_is_an_error_and_leaves_the_states():
+    """the encoder's side of the documented behaviour (psxav_hip.h): PSXHIP_EINVAL "not converged", d_states as they were, and the same
+    job with room to finish gives the serial encode -- through the one-call entry point and through a session"""
+    import torch
+    from psxavenc_amd import _lib, adpcm
+    n_units = 64
+    n = n_units * 28
+    pcm = O.synth_pcm(41, 0, 0, n, 0)                       # loud: 12000 + 6000 of two tones
+    st0 = np.array([[1000, -1000]], np.int32)
+    # without a warm-up every chunk behind the first speculates from silence: the first verify pass has something to repair as long
+    # as the true state in front of chunk 1 is not silence
+    _, after3 = O.spu_encode(pcm[:4 * 28], state=O.Chan(1000, -1000))
+    assert (after3.prev1, after3.prev2) != (0, 0)
+    d = torch.from_numpy(pcm).to("cuda:0")
+    chains = adpcm.make_chains([0], 1, n, n_units)
+    base = np.zeros(1, np.int32)
+    want_units, want_states, _ = adpcm.encode_chains_device(d, chains, base, 5, 4, d_states=torch.from_numpy(st0.copy()).to("cuda:0"))
+    want_units, want_states = want_units.cpu().numpy(), want_states.cpu().numpy()
+    d_states = torch.from_numpy(st0.copy()).to("cuda:0")
+    with pytest.raises(_lib.PsxHipError) as e:
+        adpcm.encode_chains_device(d, chains, base, 5, 4, d_states=d_states, chunk_units=4, warmup_units=0, max_passes=1)
+    assert e.value.code == _lib.PSXHIP_EINVAL and "not converged after 1" in str(e.value)
+    assert d_states.cpu().numpy().tolist() == [[1000, -1000]]
+    d_units, d_states, passes = adpcm.encode_chains_device(d, chains, base, 5, 4, d_states=d_states, chunk_units=4, warmup_units=0, max_passes=0)
+    assert passes > 1 and np.array_equal(d_units.cpu().numpy(), want_units) and np.array_equal(d_states.cpu().numpy(), want_states)
+    # ... and a session: the run that gives up leaves it usable, the next one carries on to the fixpoint
+    sess = adpcm.AdpcmSession(d, chains, base, 5, 4, chunk_units=4, warmup_units=0)
+    with pytest.raises(_lib.PsxHipError) as e:
+        sess.run(st0, max_passes=1)
+    assert e.value.code == _lib.PSXHIP_EINVAL and "not converged after 1" in str(e.value)
+    final, _ = sess.run(st0, max_passes=0)
+    assert np.array_equal(sess.d_units.cpu().numpy(), want_units) and np.array_equal(final, want_states)
+    sess.close()
+
+
+def test_small_larger_small_jobs_on_one_threads_block_cache():
+    """a one-call chunked encode builds and drops a session, whose block of device memory is parked for the thread's next call: the
+    third call takes a parked block that held another job's tables, and everything it reads there must be its own.  XA coding
+    (4 filters, 8 bits): the 12-lane instantiation"""
+    import torch
+    from psxavenc_amd import adpcm
+    for n_units in (64, 2048, 64):
+        n = n_units * 28
+        pcm = np.stack([O.synth_pcm(43, c, 0, n, k) for c, k in enumerate((0, 2))])
+        d = torch.from_numpy(pcm).to("cuda:0").reshape(-1)
+        chains = adpcm.make_chains(np.arange(2) * n, 1, n, n_units)
+        base = np.arange(2, dtype=np.int32) * n_units
+        want_units, want_states, _ = adpcm.encode_chains_device(d, chains, base, 4, 8)
+        d_units, d_states, passes = adpcm.encode_chains_device(d, chains, base, 4, 8, chunk_units=4)
+        assert passes >= 1, n_units
+        assert np.array_equal(d_units.cpu().numpy(), want_units.cpu().numpy()), n_units
+        assert np.array_equal(d_states.cpu().numpy(), want_states.cpu().numpy()), n_units
+
+
 def test_time_sharded_sessions_simulated_ranks():
     """8(e) for ADPCM: chains sharded ALONG TIME over 4 (simulated) ranks on one GPU -- each rank's session guesses its
     start state from the units before its range, ranks exchange final states until a round changes nothing"""

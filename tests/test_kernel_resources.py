@@ -129,10 +129,23 @@ def test_adpcm_kernels_build_without_scratch():
     spilled registers -- two 64-bit indices held across the warm-up loop; the verify instantiations 12 bytes nothing ever read)"""
     use = _resource_usage("adpcm_kernels.hip")
     assert sum("adpcm_chunks_kernel" in k for k in use) == 4 and any("adpcm_chains_kernel" in k for k in use), sorted(use)
+    for kernel in ("adpcm_call_kernel", "spu_pack_kernel", "adpcm_gather_final_states_kernel"):      # (the sector kernels: below)
+        assert sum(kernel in k for k in use) == 1, (kernel, sorted(use))
     for name, u in use.items():
         assert u["ScratchSize"] == "0" and u["VGPRs Spill"] == "0" and u["SGPRs Spill"] == "0", (name, u)
         if "adpcm_chunks_kernel" in name or "adpcm_chains_kernel" in name:
             assert int(u["VGPRs"]) <= 64, (name, u)       # launch bounds (64, 8): eight wavefronts per SIMD is what the chunking counts on
+
+
+@pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not installed")
+def test_sector_kernels_build_without_scratch():
+    """every __global__ of sector_kernels.hip -- exactly the three that left adpcm_kernels.hip and adpcm_decode_kernels.hip"""
+    use = _resource_usage("sector_kernels.hip")
+    assert len(use) == 3, sorted(use)
+    for kernel in ("xa_assemble_kernel", "str_video_sector_kernel", "xa_disassemble_kernel"):
+        assert sum(kernel in k for k in use) == 1, (kernel, sorted(use))
+    for name, u in use.items():
+        assert u["ScratchSize"] == "0" and u["VGPRs Spill"] == "0" and u["SGPRs Spill"] == "0", (name, u)
 
 
 @pytest.mark.skipif(not shutil.which(HIPCC), reason="hipcc not installed")
