@@ -676,6 +676,96 @@ int psxhip_str_read_host(psxhip_str_reader_t *reader, const psxhip_str_settings_
 /* revision of the reader's kernels (profiles are keyed by it) */
 const char *psxhip_str_demux_kernel_rev(void);
 
+/* ---------------------------------------------------------------- disc finisher -- */
+
+/* The step between "encoded in HBM" and "bytes a drive can read": sectors as the encoders leave them (dummy ECC, file-relative
+ * timecode, the .str EDC where the reference's muxer puts it, one track per buffer) -> interleaved raw 2352-byte Mode 2 sectors with
+ * sync, absolute BCD header, both subheader copies, EDC and, for form 1, P and Q parity (ECMA-130 / the Yellow Book).  The rules are
+ * "psxhip disc finish v1" and "psxhip disc check v1" (restated in tests/disc_ref.py).
+ *
+ * Sources: up to PSXHIP_DISC_MAX_SOURCES runs of n_sectors sectors of sector_size 2352, 2336 or 2048 bytes, sector i at sectors +
+ * i * stride (both 4-byte aligned, stride >= sector_size).  file_number (-1 .. 255) / channel_number (-1 .. 31) override the
+ * subheader's file byte and the low 5 bits of its channel byte (the top 3 bits stay); -1 keeps the source's.  A 2048-byte source has
+ * no subheader of its own: data_subheader is it (and must not have the form-2 bit 0x20 in byte 2).
+ *
+ * Schedule: period P (1 .. 64) and slot_source[P], an entry a source index or -1 (a gap).  Source s owns count_s slots.  Output sector
+ * j falls in slot q = j % P; with s = slot_source[q] and r the rank of q among s's slots it is s's sector (j / P) * count_s + r.  A gap,
+ * or a number >= n_sectors, gives the null sector: form 2, subheader 00 00 20 00, data zero, EDC like any other.
+ *
+ * Output sector j, at lba = start_lba + j (j counts from the start of the schedule, not of the call):
+ *   0x000  sync 00 FF x 10 00
+ *   0x00C  BCD minute, second, frame of lba + 150 (cdrom.c:62-65), then mode 02
+ *   0x010  subheader, twice: source bytes 0x10..0x13 (2352) / 0..3 (2336) / data_subheader (2048), with the overrides
+ *   form = bit 0x20 of the subheader's submode byte after the overrides; nothing else in the source decides it
+ *   form 2: 0x018 data 0x18..0x92B from the source; 0x92C EDC of 0x10..0x92B
+ *   form 1: 0x018 data 0x18..0x817 from the source (nothing past it is read); 0x818 EDC of 0x10..0x817; 0x81C P parity (172
+ *           bytes); 0x8C8 Q parity (104 bytes)
+ * EDC: polynomial 0xD8018001, zero init, no final xor, little-endian (cdrom.c:28-41).
+ * ECC: GF(2^8), polynomial 0x11D, alpha = 2.  d[0..2063] = sector bytes 0xC..0x81B with d[0..3] (the header) taken as zero (the
+ * Mode 2 rule), d[2064..2235] = the P bytes.
+ *   P, m = 0..85:  c_i = d[m + 86 i], i = 0..23, c_24 = P[m], c_25 = P[86 + m]; n = 26
+ *   Q, m = 0..51:  c_i = d[((m >> 1) * 86 + (m & 1) + 88 i) mod 2236], i = 0..42, c_43 = Q[m], c_44 = Q[52 + m]; n = 45
+ * The parity is the pair with sum c_i = 0 and sum alpha^(n-1-i) c_i = 0: over the data symbols A = sum c_i, B = sum alpha^(n-1-i) c_i,
+ * the first parity byte is (A ^ B) / 3 and the second is that ^ A. */
+#define PSXHIP_DISC_MAX_SOURCES 64
+#define PSXHIP_DISC_MAX_PERIOD 64
+#define PSXHIP_DISC_LBA_LIMIT 450000     /* lba + 150 stays below it: the minute is two BCD digits */
+
+typedef struct {
+	const uint8_t *sectors;      /* device memory (psxhip_disc_finish_device) or host memory (psxhip_disc_finish_host); not read by psxhip_disc_plan */
+	int64_t stride;              /* bytes from one sector to the next */
+	int32_t n_sectors;
+	int32_t sector_size;         /* 2352, 2336 or 2048 */
+	int32_t file_number;         /* -1: keep the source's byte */
+	int32_t channel_number;      /* -1: keep the source's byte */
+	uint8_t data_subheader[4];   /* 2048-byte sources only */
+	int32_t reserved;
+} psxhip_disc_source_t;
+
+typedef struct {
+	int32_t period;              /* 1 .. PSXHIP_DISC_MAX_PERIOD */
+	int32_t start_lba;           /* lba of output sector 0 of the schedule (not read by psxhip_disc_plan) */
+	int32_t slot_source[PSXHIP_DISC_MAX_PERIOD];   /* [period]: a source index, or -1 for a gap */
+} psxhip_disc_layout_t;
+
+/* Sectors of the whole schedule: period * max over the sources of ceil(n_sectors / count); 0 without sectors.  Host-only (no device
+ * is touched).  PSXHIP_EINVAL for a layout or a source outside the rules above, or when a source with sectors owns no slot. */
+int64_t psxhip_disc_plan(const psxhip_disc_layout_t *layout, const psxhip_disc_source_t *sources, int n_sources);
+
+/* Sectors first_out .. first_out + n_out - 1 of the schedule -> d_out (n_out x 2352 bytes, 4-byte aligned, overlapping no source), so
+ * a large image can be made in pieces.  Refused (PSXHIP_EINVAL, before any device call) for arguments outside the rules above,
+ * start_lba < 0, or a last sector with lba + 150 >= PSXHIP_DISC_LBA_LIMIT.  Asynchronous on `stream`; nothing is read back. */
+int psxhip_disc_finish_device(int device, const psxhip_disc_layout_t *layout, const psxhip_disc_source_t *sources, int n_sources,
+                              uint8_t *d_out, int64_t first_out, int64_t n_out, void *stream);
+
+/* The inverse statement, defined for arbitrary bytes: per 2352-byte sector status bits, never a fault, no correction. */
+enum {
+	PSXHIP_DISC_SYNC = 1,          /* bytes 0..11 are not the sync */
+	PSXHIP_DISC_HEADER = 2,        /* mode is not 2, or the MSF is not the BCD of lba + 150 (lba = start_lba + the sector's index);
+	                                  with start_lba == -1: mode is not 2, or a nibble of the MSF is above 9 */
+	PSXHIP_DISC_SUBHEADER = 4,     /* the two subheader copies differ */
+	PSXHIP_DISC_EDC = 8,           /* the stored word differs from the computed one; the form is bit 0x20 of byte 0x12 */
+	PSXHIP_DISC_ECC_P = 16,        /* form 1 only: a P codeword has a non-zero syndrome, the header taken as zero */
+	PSXHIP_DISC_ECC_Q = 32,        /* form 1 only: ... a Q codeword */
+	PSXHIP_DISC_EDC_ABSENT = 64    /* form 2 and the stored word is 0; set instead of PSXHIP_DISC_EDC */
+};
+typedef struct {
+	int32_t n_sectors, n_form1, n_form2;
+	int32_t n_bad;               /* sectors with any bit set */
+	int32_t n_sync, n_header, n_subheader, n_edc, n_ecc_p, n_ecc_q, n_edc_absent;   /* sectors per bit */
+	int32_t reserved;
+} psxhip_disc_summary_t;
+/* d_status (optional) [n_sectors] gets the bits; *d_summary (device memory) is overwritten.  start_lba >= -1, and with start_lba >= 0
+ * the last lba + 150 < PSXHIP_DISC_LBA_LIMIT.  Pointers 4-byte aligned; asynchronous on `stream`. */
+int psxhip_disc_check_device(int device, const uint8_t *d_image, int64_t n_sectors, int64_t start_lba, int32_t *d_status,
+                             psxhip_disc_summary_t *d_summary, void *stream);
+
+/* psxhip_disc_finish_device for sources and an image in host memory: H2D of the sources, finish, D2H; returns when `out` is written. */
+int psxhip_disc_finish_host(int device, const psxhip_disc_layout_t *layout, const psxhip_disc_source_t *sources, int n_sources,
+                            uint8_t *out, int64_t first_out, int64_t n_out);
+/* revision of the finisher's kernels (profiles are keyed by it) */
+const char *psxhip_disc_kernel_rev(void);
+
 /* ---------------------------------------------------------------- SPU / VAG / SPUI / VAGI files ---- */
 
 /* The reference's encode_file_spu / encode_file_spui (psxavenc/filefmt.c:212-389, .vag header :95-162) for PCM that is

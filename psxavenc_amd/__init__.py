@@ -14,3 +14,5 @@ from .adpcm_decode import (adpcm_sse, decode_chains_chunked, decode_chains_devic
                            xa_decode_streams, xa_disassemble)
 from . import strdemux  # noqa: E402,F401  (strdemux.kernel_rev(): the revision of the STR reader's kernels)
 from .strdemux import StrReader  # noqa: E402,F401
+from . import disc  # noqa: E402,F401  (disc.kernel_rev(): the revision of the disc finisher's kernels)
+from .disc import disc_check, disc_finish, disc_plan  # noqa: E402,F401
