@@ -7,7 +7,9 @@ Per 8x8 block, levels lv[0..63] in zig-zag order, quant scale s (the header's 16
   dequantise   F8[0]  = clamp(16 * lv[0],                 -SAT, SAT - 1)          DC x 2, with three fraction bits
                F8[ri] = clamp(lv[z] * Q[ri] * s,          -SAT, SAT - 1)          ri = raster position of scan position z >= 1
                         (level x Q x scale / 8 exactly, kept as eighths; SAT = 2^14: |coefficient| < 2048, twice what an 8x8
-                        block of 8-bit pixels can produce, so saturation touches no stream an encoder made)
+                        block of 8-bit pixels can produce, so saturation touches no stream an encoder made.  The saturating
+                        range is exercised all the same, not only argued: tests/mdec_foreign_streams.py writes streams whose
+                        coefficients saturate, and statement and kernel are held to a float64 IDCT of the clamped values there)
   rows         T[v][x] = (sum_u F8[v][u] * C[u][x] + 2^14) >> 15                   two fraction bits are kept
   columns      P[y][x] = (sum_v T[v][x]  * C[v][y] + 2^15) >> 16
   pixel        clamp(P + 128, 0, 255)
@@ -139,6 +141,23 @@ def error_bound(f8):
 def pixel_bound(f8):
     """largest |device pixel - lrint(real pixel)| the statement allows, per block"""
     return np.floor(error_bound(f8)).astype(np.int64) + 1
+
+
+def real_pixels(f8):
+    """clip(rint(real IDCT of F8 / 8 + 128), 0, 255) in float64, (blocks, 8, 8) int64: what the integers stand for, F8 as dequantise()
+    gives it, saturated coefficients included"""
+    cs = real_matrix()
+    return np.clip(np.rint(np.einsum("bvu,ux,vy->byx", np.asarray(f8, np.float64) / 8.0, cs, cs) + 128.0), 0, 255).astype(np.int64)
+
+
+def saturating_blocks(levels, scale):
+    """per block: a coefficient is clamped, i.e. dequantise() differs from the plain product"""
+    lv = np.asarray(levels, np.int64).reshape(-1, 64)
+    zz = zagzig()
+    f = np.zeros_like(lv)
+    f[:, zz] = lv * QUANT[zz] * int(scale)
+    f[:, 0] = lv[:, 0] * 16
+    return (f.reshape(-1, 8, 8) != dequantise(lv, scale)).any(axis=(1, 2))
 
 
 # ---------------------------------------------------------------- SSE
