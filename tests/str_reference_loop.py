@@ -132,3 +132,71 @@ def encode_file_str(fmt, codec, w, h, fps_num, fps_den, cd_speed, frames, pcm, c
         sector_count += 1
     stream = np.stack(out) if out else np.zeros((0, sector_size), np.uint8)
     return stream, enc.quant_scale_sum, enc.frame_index
+
+
+def encode_stream_complete(fmt, codec, w, h, fps_num, fps_den, cd_speed, frames, pcm, channels=2, freq=37800, bits=4,
+                           trailing_audio=False, xa_file=1, xa_channel=0, video_id=0x8001, xa_encode=None):
+    """PSXHIP_STR_TAIL_COMPLETE: the sector loop of encode_file_str (filefmt.c:450-503) over the oracle's restatements with
+    the end-of-input rules replaced -- every frame is encoded, the stream ends with the last frame's last sector, EOF on the
+    last audio sector only.  The checker for both muxers' COMPLETE tail (the reference's own tail is encode_file_str above).
+    `pcm` must hold a whole sector's samples for every audio slot of the stream.  Returns (sectors, quant_scale_sum)."""
+    xa_encode = xa_encode or O.xa_encode
+    n_frames = frames.shape[0]
+    ofmt = {6: O.FMT_STR, 7: O.FMT_STRCD, 9: O.FMT_STRV}[fmt]
+    oxs = O.XaSettings(1 if fmt == 7 else 0, 1 if channels == 2 else 0, freq, bits, xa_file, xa_channel)
+    ssz = O.lib().orc_xa_sector_size(oxs)
+    if channels:
+        interleave = O.lib().orc_xa_sector_interleave(oxs) * cd_speed
+        sps = O.lib().orc_xa_samples_per_sector(oxs)
+        vspb = interleave - 1
+    else:
+        interleave, sps, vspb = 1, 0, 1
+    base, den = 75 * cd_speed * vspb * fps_den, interleave * fps_num
+    cap = 2016 * -(-base // den)
+    ofo = np.zeros(cap, np.uint8)
+    ost = O.StrState(0, 0, 0, base, 0, den, 0, 0, ofo.ctypes.data)
+    oastate = None
+    out = []
+    audio_at = []
+    frame_cursor, audio_cursor, sector_count = 0, 0, 0
+    while True:
+        if frame_cursor >= n_frames and ost.frame_data_offset >= ost.frame_max_size:
+            break                        # the for-condition of filefmt.c:450 with all input consumed
+        if channels == 0:
+            is_video = True
+        elif trailing_audio:
+            is_video = (sector_count % interleave) < vspb
+        else:
+            is_video = (sector_count % interleave) > 0
+        want = np.zeros(2352, np.uint8)
+        if is_video:
+            if fmt == 7:
+                O.lib().orc_cdrom_init_sector(O.ptr(want, O.u8p), sector_count, 1)
+                want[16:20] = [xa_file, xa_channel & 0x1F, 0x08 | 0x40, 0]
+                want[20:24] = want[16:20]
+            elif fmt == 6:
+                want[0:4] = [xa_file, xa_channel & 0x1F, 0x08 | 0x40, 0]
+                want[4:8] = want[0:4]
+            fr = frames[min(frame_cursor, n_frames - 1)]
+            used = O.lib().orc_mdec_encode_sector_str(C.byref(ost), codec, w, h, ofmt, video_id, O.ptr(fr, O.u8p), O.ptr(want, O.u8p))
+            assert used >= 0
+            O.lib().orc_cdrom_calculate_checksums(O.ptr(want, O.u8p), 1)
+            frame_cursor += used
+        else:
+            chunk = pcm[channels * audio_cursor:]
+            w_, oastate = xa_encode(oxs, chunk, sps, lba=sector_count, state=oastate)
+            want[:ssz] = w_[:ssz]
+            audio_cursor += sps
+            audio_at.append(len(out))
+        out.append(want[:ssz].copy())
+        sector_count += 1
+    # the muxed stream ends with the last frame's last sector; the last audio sector carries EOF (adpcm.c:334-340)
+    while audio_at and audio_at[-1] >= len(out):
+        audio_at.pop()
+    stream = np.stack(out) if out else np.zeros((0, ssz), np.uint8)
+    if audio_at:
+        k = audio_at[-1]
+        sub = 0x12 if fmt == 7 else 0x02
+        stream[k, sub] |= 0x80
+        stream[k, sub + 4] |= 0x80
+    return stream, ost.quant_scale_sum
