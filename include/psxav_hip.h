@@ -175,7 +175,9 @@ int psxhip_mdec_query_geometry(int device, int codec, int width, int height, int
  * entry to the end of its prologue << 8 | ticks to the end of its first frame << 32. */
 #define PSXHIP_MDEC_STATS_PHASE0 (PSXHIP_MDEC_STATS + 4 * PSXHIP_MDEC_TRACE_GROUPS)
 /* and one word per frame of the last launch (the first PSXHIP_MDEC_TRACE_FRAMES frames): first guess | first checkpoint
- * verdict << 8 | answer << 16 | passes << 24 */
+ * verdict << 8 (7 bits) | bit 15: the frame's last pass stopped counting the scale below at its checkpoint (v2: its count was a
+ * mixed lower bound) | answer << 16 | passes << 24 | from bit 32 one byte per pass for the first four: emit scale, or count
+ * scale | 0x40; | 0x80 stopped at the checkpoint */
 #define PSXHIP_MDEC_TRACE_FRAMES 2048
 #define PSXHIP_MDEC_STATS_FRAME0 (PSXHIP_MDEC_STATS_PHASE0 + 16)
 #define PSXHIP_MDEC_STATS_TOTAL (PSXHIP_MDEC_STATS_FRAME0 + PSXHIP_MDEC_TRACE_FRAMES)

@@ -66,6 +66,11 @@ constexpr int kLeaveWord = 8;
 constexpr int kLeaveWrongShift = 32, kLeaveTriedShift = 48;
 constexpr unsigned kTrustCap = 63u;
 constexpr float kCkMargin = 1000.0f;     // quarter-pass checkpoint: how far (thousandths of its standard error) a projection has to be on the wrong side
+// v2: a pass that counts at the scale below stops counting at its checkpoint when the sample says the MIXED bound (mdec_search.h:
+// mdec_search_note_bound) will prove that scale and everything below it too long anyway.  The judge tells the wavefronts through the
+// ticket they draw in every macroblock: this bit set in S_MB_NEXT (below the checkpoint's "stop", 0x40000000; masked off a drawn ticket).
+constexpr int kStopCount = 0x20000000;
+constexpr float kStopCountFactor = 2.0f;   // ... when the projected bound clears the limit by this many standard errors (decides passes, never results)
 constexpr int kNoTicket = 0x7FFFFFFF;   // S_FRAME of a group that has run out of fresh-frame tickets (end_of_frame): it takes frames from the retry queue
 constexpr int kPilotWord = 10;           // (64 bits) what the groups learned about the PILOT's guesses: wrong | tried << 32, added before the group counts itself out
 constexpr int kDistrustWord = 4;         // hint[kDistrustWord]: the launches before this one found foreign hints wrong more than one time in four (shared by the context's lanes, like the hint)
@@ -175,7 +180,7 @@ enum {
     S_RETRY,            // this frame came from the retry queue: the scale to start from (0: a fresh frame; -1: the queue is empty)
     S_DEFER,            // 1: the frame goes to the retry queue instead of into another pass here; 2: it starts over from the pilot (S_REPILOT)
     S_PILOTED,          // the pilot has run for this frame (its guess is a measurement, not somebody else's answer)
-    S_SPARE0,           // (unused)
+    S_CNT_BOUND,        // the pass (its number) whose count is a lower bound, not a total: counting stopped at its checkpoint (kStopCount)
     S_SEARCH,           // MdecSearch (14 ints)
     S_PILOT_SCALE0 = S_SEARCH + 14,    // [kPilotMax]
     S_PILOT_BITS0 = S_PILOT_SCALE0 + kPilotMax,   // [kPilotMax]
@@ -1376,6 +1381,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         };
         unsigned long long trace = 0;       // diagnostics: the first four passes (of the last attempt): emit scale, or count scale | 0x40; | 0x80 stopped at the checkpoint
         int n_pass = 0, first_abort = 0, guess0 = 0;      // (first_abort, guess0: diagnostics)
+        bool stopped_last = false;                         // diagnostics: the frame's last pass stopped counting at its checkpoint
         int guess;
         MdecSearch* srch = (MdecSearch*)&L.scalars[S_SEARCH];
         group_sync(1);
@@ -1520,7 +1526,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             fetch_at(cur_o.x & 0x7FFFFFFFu, cur_o.y & 0xFFFFu);
             const QuantK kc = make_quant(lc.quant, count_scale ? count_scale : 1);
             const QuantK ke = make_quant(lc.quant, emit_scale ? emit_scale : 1);
-            int acc_cnt = 0;             // per lane: bits | deficit << 16 over this wavefront's macroblocks (count scale)
+            // v2: a macroblock is counted while the ticket drawn last is below this (0: the pass does not count; kStopCount: until the judge sets that bit)
+            // (a value of its own in a scalar register: seen through, the compiler tests "does the pass count" and the ticket's bit apart --
+            //  five scalar instructions per macroblock where this is one compare)
+            uint32_t cnt_gate = CODEC == 0 && count_scale ? (uint32_t)kStopCount : 0u;
+            if (CODEC == 0) asm volatile("" : "+s"(cnt_gate));
+            int acc_cnt = 0;             // per lane: bits | deficit << 16 over this wavefront's macroblocks (count scale; v2, uncounted macroblocks: of the emitted codes)
             int acc_edef = 0;            // per lane: deficit over the emitted codes
             int n_codes = 0;             // wave-uniform: codes emitted (AC codes + DC slots)
             int emit_bits = 0, mb_done = 0;  // wave-uniform
@@ -1608,11 +1619,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         // (NOTEBOOK section 3, Mapping): content whose answer flips between neighbouring scales gains 14 %
                         // over a fixed 5 % margin, stable content is unaffected).
                         int margin = (limit_bits - fixed_bits) / 50;
+                        float se = -1.0f;
                         if (emit_scale && records_ok && done > 1 && done < nmb) {
                             const float n = (float)done, mean = (float)ck_s1 / n;      // of x = bits >> 2
                             float var = (float)ck_sq / n - mean * mean;
                             var = var > 0.0f ? var : 0.0f;
-                            const float se = 4.0f * __builtin_sqrtf(var * n * (1.0f - n / (float)nmb)) * ((float)nmb / n);
+                            se = 4.0f * __builtin_sqrtf(var * n * (1.0f - n / (float)nmb)) * ((float)nmb / n);
                             margin = (int)(se * kCkMargin * 0.001f);      // (two roundings, as when the 1000 was a kernel argument: the margin decides pass counts)
                         }
                         int g = mdec_search_checkpoint_bits(*srch, count_scale, (int)pa, emit_scale, (int)pb, limit_bits, fixed_bits, margin);
@@ -1634,6 +1646,22 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             L.scalars[S_ABORT] = g | (n_pass << 8);
                             L.scalars[S_ABORTS_LEFT] = L.scalars[S_ABORTS_LEFT] - 1;
                             atomicMax(&L.scalars[S_MB_NEXT], 0x40000000);
+                        } else if (CODEC == 0 && count_scale && emit_scale && se >= 0.0f) {
+                            // The pass goes on.  Does it have to go on COUNTING?  The count is only there to prove "no scale <= count_scale
+                            // fits", and any mix of (AC bits - deficit at the count scale) over some macroblocks and (AC bits - deficit at
+                            // the emit scale) over the others is a lower bound for all those scales.  Projected from the sample: what it
+                            // counted, plus its emitted AC bits - deficit (a v2 macroblock's stream: 72 bits of DC and end-of-block codes)
+                            // scaled up to the macroblocks still to come.  The standard error is that of the emit projection.
+                            const long long counted = (long long)L.scalars[S_CNT_F] - L.scalars[S_CNT_D];
+                            const long long emitted = (long long)L.scalars[S_EMIT_BITS] - 72ll * done - L.scalars[S_EMIT_D];
+                            const long long bound = fixed_bits + counted + emitted * (nmb - done) / done;
+                            // (In a small frame every remaining ticket may be drawn already when the flag is set: the pass's sums are then a
+                            //  complete, exact count at count_scale and are still reported as a bound -- no fail bit, no model point, and a
+                            //  pass that only counts may follow.  A pass at the worst, never a result.)
+                            if ((float)(bound - limit_bits) > kStopCountFactor * se) {
+                                L.scalars[S_CNT_BOUND] = n_pass;
+                                atomicOr(&L.scalars[S_MB_NEXT], kStopCount);
+                            }
                         }
                     }
                 }
@@ -1657,7 +1685,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 }
                 cur_t = nxt_t;
                 cur_o = nxt_o;
-                nxt_t = __builtin_amdgcn_readfirstlane(drawn);
+                const uint32_t drawn_u = (uint32_t)__builtin_amdgcn_readfirstlane(drawn);
+                nxt_t = CODEC == 0 ? (int)(drawn_u & ~(uint32_t)kStopCount) : (int)drawn_u;
                 nxt_o = order_at(nxt_t);
                 if (!valid) continue;
                 mb_done++;
@@ -1738,7 +1767,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         dense = n_low > 128;
                     }
                     if (!dense) {
-                        count = build_list(low_off, low_span);
+                        // (v2: a macroblock that is not counted lists at the emit scale, also in a pass that counts)
+                        if constexpr (CODEC == 0 && !cs) count = build_list(emit_off, emit_span);
+                        else count = build_list(low_off, low_span);
                         if (cs) {
                             prev_len = count;
                             dense = count > 128;
@@ -1851,6 +1882,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             code = len == BS_ESCAPE_BITS ? esc : code;
                         }
                         deficit = (int)((entry >> BS_LUT_DEFICIT_SHIFT) & 0xFu);
+                        // v2, a macroblock that is not counted: its emitted AC codes' bits | deficit << 16 go where the count's would
+                        // (before the DC slots and end-of-block bits come in: those are in fixed_bits) -- the pass's sums are then the mixed bound
+                        // (also in a v2 pass that does not count at all -- two instructions per chunk whose sums nobody flushes: a test of
+                        //  the gate word here would cost the counting passes as much and a scalar register the 12-wavefront shape lacks)
+                        if (CODEC == 0 && !cs) cnt16 = len | (deficit << 16);
                         if (CODEC == 0) {
                             // v2 DC slot: the entry carries the quantised DC; 10 bits (mdec.c:451-453), every slot but the
                             // macroblock's first also carries the previous block's end-of-block code
@@ -1975,13 +2011,20 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             put_codes(base_dw, pos + (uint32_t)(incl - len), len, code);
                             pos += (uint32_t)__builtin_amdgcn_readlane(incl, 63);
                             acc_edef += deficit;
+                            if (CODEC == 0 && !cs) acc_cnt += cnt16;
                             n_codes += nc;
                         }
                     }
                     wave_sync();   // the list is overwritten by the next macroblock's tiles
                 };
-                if (count_scale) emit_mb(yes);
-                else emit_mb(no);
+                if (CODEC == 0) {
+                    // (the flag of the ticket drawn LAST, not of the macroblock's own: every split of the frame gives a valid bound)
+                    if (drawn_u < cnt_gate) emit_mb(yes);
+                    else emit_mb(no);
+                } else {
+                    if (count_scale) emit_mb(yes);
+                    else emit_mb(no);
+                }
             }
             // outside the passes a group runs short, latency-bound phases (decisions, scans, merge): let them cut ahead of the
             // partner group's VALU stream instead of queueing behind it
@@ -1992,6 +2035,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             aborted = (verdict >> 8) == n_pass;          // (this pass's verdict; an older one is stale)
             if (STATS && tid == 0 && aborted && !first_abort) first_abort = verdict & 0xFF;
             if (STATS && aborted && n_pass <= 4) trace |= 0x80ull << (24 + 8 * n_pass);
+            if (STATS && tid == 0) stopped_last = CODEC == 0 && count_scale && !aborted && L.scalars[S_CNT_BOUND] == n_pass;
             if (scan_early && wid == 1 && emit_scale && !aborted) scan_offsets(lane);
             if (tid == 0) {
                 MdecSearch st = *srch;
@@ -2048,7 +2092,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         (void)hand_on(np);
                     }
                 } else {
-                if (count_scale) {
+                bool bounded = false;
+                if (CODEC == 0 && count_scale && L.scalars[S_CNT_BOUND] == n_pass) {
+                    bounded = true;
+                    // counting stopped at the checkpoint: the sums are the mixed bound for all scales <= count_scale, nobody's total
+                    mdec_search_note_bound(st, count_scale, L.scalars[S_CNT_F] - L.scalars[S_CNT_D] + fixed_bits, limit_bits);
+                } else if (count_scale) {
                     const int tb = L.scalars[S_CNT_F] + fixed_bits;
                     mdec_search_note(st, count_scale, tb, tb - L.scalars[S_CNT_D], limit_bits);
                 }
@@ -2058,7 +2107,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     st.staged = L.scalars[S_STG_NEXT] > job.stg_words ? 0 : emit_scale;       // (the staging area ran out during this pass)
                     L.scalars[S_TOTAL_BITS] = tb;
                 }
-                const MdecPass np = mdec_search_next(st, guess, limit_bits, fixed_bits);
+                const MdecPass np = CODEC == 0 && bounded ? mdec_search_next_after_bound(st, count_scale, guess, limit_bits, fixed_bits)
+                                                          : mdec_search_next(st, guess, limit_bits, fixed_bits);
                 *srch = st;
                 L.scalars[S_PASS_COUNT] = np.count_scale;
                 L.scalars[S_PASS_EMIT] = np.emit_scale;
@@ -2098,7 +2148,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         n_done++;
         if (STATS) { n_pass += carry_pass; carry_pass = 0; }      // (a frame sent back to the pilot: its first attempt's pass counts)
         if (STATS && tid == 0 && f < PSXHIP_MDEC_TRACE_FRAMES)      // per-frame record: first guess | first abort verdict << 8 | answer << 16 | passes << 24
-            job.stats[PSXHIP_MDEC_STATS_FRAME0 + f] = (unsigned long long)(guess0 & 0xFF) | (unsigned long long)(first_abort & 0xFF) << 8 |
+            job.stats[PSXHIP_MDEC_STATS_FRAME0 + f] = (unsigned long long)(guess0 & 0xFF) | (unsigned long long)(first_abort & 0x7F) << 8 | (stopped_last ? 0x8000ull : 0ull) |
                                                       (unsigned long long)(L.scalars[S_RESULT] & 0xFF) << 16 | (unsigned long long)(n_pass & 0xFF) << 24 | trace;
         if (STATS && tid == 0) {
             pass_sum += (unsigned)n_pass;

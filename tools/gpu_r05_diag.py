@@ -111,7 +111,8 @@ def stats_run(bb, warm):
     enc.close()
     r = {"frames": s[0], "passes_per_frame": round(s[1] / max(1, s[0]), 4), "passes_hist_0_1_2_3_4_5plus": s[2:8]}
     fr = np.array(s[8 + 4096 + 16:8 + 4096 + 16 + N], dtype=np.int64)
-    guess, ab, ans, np_ = fr & 0xFF, (fr >> 8) & 0xFF, (fr >> 16) & 0xFF, (fr >> 24) & 0xFF
+    guess, ab, ans, np_ = fr & 0xFF, (fr >> 8) & 0x7F, (fr >> 16) & 0xFF, (fr >> 24) & 0xFF
+    r["last_pass_stopped_counting_at_its_checkpoint"] = int(((fr >> 15) & 1).sum())      # (v2, mdec-k3.9: the count became a mixed bound)
     tr = ["/".join(("%d%s%s" % (b & 0x3F, "c" if b & 0x40 else "", "!" if b & 0x80 else "")) for b in [(int(x) >> (32 + 8 * k)) & 0xFF for k in range(4)] if b) for x in fr]
     r["first_guess_right"] = int((guess == ans).sum())
     r["first_guess_off_by_one"] = int((np.abs(guess - ans) == 1).sum())
