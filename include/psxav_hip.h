@@ -508,7 +508,7 @@ enum {
 };
 
 typedef struct {
-	int32_t format;             /* format_t: 6 = STR (2336-byte sectors), 7 = STRCD (2352), 9 = STRV */
+	int32_t format;             /* format_t: 6 = STR (2336-byte sectors), 7 = STRCD (2352), 9 = STRV (2048), 8 = STRSPU (2048, below) */
 	int32_t video_codec;        /* bs_codec_t */
 	int32_t video_width, video_height;
 	int32_t str_fps_num, str_fps_den;
@@ -516,18 +516,30 @@ typedef struct {
 	int32_t str_video_id;       /* 0x8001 */
 	int32_t trailing_audio;     /* FLAG_STR_TRAILING_AUDIO: audio sector last in each block instead of first */
 	int32_t audio_channels;     /* 0 = no audio stream (all sectors are video), 1, 2 */
-	int32_t audio_frequency;    /* 18900 / 37800 */
-	int32_t audio_bit_depth;    /* 4 / 8 */
-	int32_t audio_xa_file, audio_xa_channel;
+	int32_t audio_frequency;    /* 18900 / 37800; STRSPU: any rate the CD speed can carry */
+	int32_t audio_bit_depth;    /* 4 / 8 (STRSPU: ignored) */
+	int32_t audio_xa_file, audio_xa_channel;   /* (STRSPU: ignored) */
 	int32_t tail_mode;          /* PSXHIP_STR_TAIL_* */
-	int32_t reserved;
+	int32_t strspu_options;     /* STRSPU: audio chunk id | PSXHIP_STRSPU_*; any other bit set is PSXHIP_EINVAL.  Formats 6 / 7 / 9 ignore it */
 } psxhip_str_settings_t;
+
+/* Format 8, STRSPU ("psxhip STRSPU v1"): .str video chunks interleaved with chunks of SPU-ADPCM audio in plain
+ * 2048-byte sectors -- the format the reference lists and leaves unimplemented (filefmt.c:522-631).  A video sector is STRV's.  An
+ * audio sector is a 32-byte chunk header (60 01, the audio chunk id, index 0 of 1, the chunk's number from 1, 2016, channels, lane
+ * bytes L, frequency, first sample, flags) and 126 SPU blocks: B = 126 / channels per channel, channel c's lane at 0x20 + c * L,
+ * L = 16 B; the lanes are an SPUI file of interleave L (leading dummy block, loop flag or trap block at the end of a chunk,
+ * filefmt.c:323-371).  Audio sectors are the share audio_frequency / (28 B * 75 * str_cd_speed) of the stream, which must be below 1:
+ * among the first n sectors ceil(n p / q) are audio (floor with trailing_audio).  Only PSXHIP_STR_TAIL_COMPLETE is defined.  With
+ * audio_channels 0 the stream is byte for byte the STRV stream. */
+#define PSXHIP_STRSPU_ID_MASK 0xFFFF             /* bits 0-15: the audio chunk id (args_t.str_audio_id, default 0x0001), taken literally */
+#define PSXHIP_STRSPU_LOOP 0x10000               /* FLAG_SPU_ENABLE_LOOP (-L): every chunk's last block carries the repeat flag, no trap block */
+#define PSXHIP_STRSPU_NO_LEADING_DUMMY 0x20000   /* -D: the lanes do not start with a silent block */
 
 typedef struct {
 	int32_t n_sectors;
 	int32_t n_video_sectors, n_audio_sectors;   /* audio slots, incl. those with no samples left */
-	int32_t sector_size;        /* 2336 or 2352 */
-	int32_t interleave;         /* sectors per block: 1 audio + (interleave - 1) video */
+	int32_t sector_size;        /* 2336, 2352 or 2048 */
+	int32_t interleave;         /* sectors per block: 1 audio + (interleave - 1) video (STRSPU: q / p when that is whole, else 0) */
 	int32_t audio_samples_per_sector;   /* per channel */
 	int32_t max_frame_size;     /* largest per-frame budget */
 	int32_t n_frames_encoded;   /* frames that are part of the stream (REFERENCE tail: n_frames - frames_needed, or fewer when
@@ -579,6 +591,20 @@ int psxhip_str_encode_device(psxhip_str_ctx_t *ctx, const psxhip_str_settings_t 
                              size_t frames_stream_stride, int n_frames, const int16_t *d_pcm, int64_t pcm_stream_stride,
                              int64_t pcm_samples_per_channel, uint8_t *d_out, size_t out_stream_stride, psxhip_str_plan_t *plan,
                              void *stream);
+
+/* The audio sector builder of format 8 on its own (as psxhip_xa_assemble_device is for XA): n_sectors audio sectors of 2048 bytes per
+ * stream from SPU unit records.  d_units: per stream n_sectors * 126 records of 16 bytes (PSXHIP_ADPCM_RECORD_BYTES_4BIT), unit u of
+ * channel c at record u * channels + c (the order of one chain per channel with unit_stride = channels), 16-byte aligned, the streams
+ * units_stream_stride bytes (a multiple of 16) apart.  A channel has U = n_sectors * 126 / channels - 1 units (one more with
+ * PSXHIP_STRSPU_NO_LEADING_DUMMY: no block is spent on the dummy); records behind them are not read.  n_sectors is the stream's whole
+ * audio: the last sector carries the trap block and the last-chunk flag.  Sector k of stream i goes to d_out + i * out_stream_stride
+ * + d_dst_sector[k] * 2048 (d_dst_sector NULL: dense, slot k); d_out and out_stream_stride 4-byte aligned.  channels 1 or 2;
+ * options as strspu_options.  Asynchronous on `stream`; nothing is read back. */
+int psxhip_strspu_audio_sectors_device(int device, const uint8_t *d_units, int n_sectors, int channels, int frequency,
+                                       uint32_t options, int n_streams, size_t units_stream_stride, uint8_t *d_out,
+                                       const int32_t *d_dst_sector, size_t out_stream_stride, void *stream);
+/* revision of the STRSPU audio sector kernel */
+const char *psxhip_strspu_kernel_rev(void);
 
 /* ---------------------------------------------------------------- STR / STRCD / STRV reader -- */
 

@@ -38,6 +38,39 @@ static inline bool str_sector_geometry(int format, int* sector_size, int* sub_at
     return false;
 }
 
+// format 8 (STRSPU, "psxhip STRSPU v1"): 2048-byte sectors; an audio sector holds 126 SPU blocks behind a
+// 32-byte chunk header, shared by the channels in lanes of L bytes.  Audio sectors are a share p / q < 1 of the stream:
+// audio_frequency / (samples per channel per sector x 75 sectors a second x CD speed), reduced.
+struct StrspuLayout {
+    int channels;
+    int blocks;                 // B: SPU blocks per channel per audio sector
+    int lane_bytes;             // L = 16 B
+    int samples_per_sector;     // spc = 28 B, per channel
+    int64_t p, q;               // the audio share of the sectors; p >= q: the rate does not fit the CD speed
+};
+
+// channels 1 or 2, frequency > 0, cd_speed 1 or 2 (the caller's checks)
+static inline StrspuLayout strspu_layout(int channels, int frequency, int cd_speed) {
+    StrspuLayout x;
+    x.channels = channels;
+    x.blocks = 126 / channels;
+    x.lane_bytes = 16 * x.blocks;
+    x.samples_per_sector = 28 * x.blocks;
+    int64_t a = frequency, b = (int64_t)x.samples_per_sector * 75 * cd_speed;
+    x.p = a;
+    x.q = b;
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    x.p /= a;
+    x.q /= a;
+    return x;
+}
+
+// a(n): audio sectors among the first n sectors -- leading audio never falls behind (ceil), trailing audio never runs ahead (floor).
+// Sector n is an audio sector iff a(n + 1) > a(n).  n < 2^31 and p < q <= 2 x 28 x 126 x 75: the product stays far inside 64 bits.
+static inline int64_t strspu_audio_before(const StrspuLayout& x, bool trailing, int64_t n) {
+    return trailing ? n * x.p / x.q : (n * x.p + x.q - 1) / x.q;
+}
+
 // n_streams planar streams, one chain each: stream i reads from sample i * stream_stride on, its records follow stream i - 1's
 static inline void fill_planar_chains(psxhip_adpcm_chain_t* chains, int32_t* unit_base, int n_streams, int64_t stream_stride, int pitch,
                                       int sample_limit, int n_units) {

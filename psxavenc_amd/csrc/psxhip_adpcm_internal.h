@@ -1,5 +1,5 @@
 // psxhip_adpcm_internal.h -- glue between the ADPCM / sector C-ABI layer (psxhip_adpcm_encode.cpp, psxhip_adpcm_decode.cpp,
-// psxhip_audio_api.cpp, psxhip_str.cpp) and its kernels (adpcm_kernels.hip, adpcm_decode_kernels.hip, sector_kernels.hip): the job
+// psxhip_audio_api.cpp, psxhip_str.cpp) and its kernels (adpcm_kernels.hip, adpcm_decode_kernels.hip, sector_kernels.hip, strspu_kernels.hip): the job
 // struct every kernel takes, declared once, and the launch functions.  A launch function fills nothing but the launch geometry.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -157,6 +157,24 @@ typedef struct {
 	uint32_t eof_edc_delta; /* EDC of an all-zero span with 0x80 at sector bytes 18 and 22 */
 } psxhip_xa_dis_job_t;
 hipError_t psxhip_xa_disassemble_launch(const psxhip_xa_dis_job_t *j, void *stream);
+
+/* ---- strspu_kernels.hip: the audio sectors of a muxed STRSPU stream ("psxhip STRSPU v1") ---- */
+/* bumped with every change to strspu_kernels.hip */
+#define PSXHIP_STRSPU_KERNEL_REV "strspu-k1.0"
+/* strspu_audio_sector_kernel: one 128-lane workgroup per 2048-byte sector, one lane per 16 bytes: two for the chunk header, 126 for
+ * the SPU blocks.  Record (u * channels + c) of a stream's units is unit u of channel c's chain (fill_interleaved_chains); the stream
+ * holds n_sectors * 126 records, 16 bytes apart, 16-byte aligned.  Sector k goes to slot dst_sector[k] of its stream's output;
+ * n_sectors is the K of the format: the last sector carries the trap block and the "last chunk" flag */
+typedef struct {
+	const uint8_t *units;
+	int n_sectors, channels, frequency;
+	uint32_t options;           /* strspu_options of psxhip_str_settings_t */
+	uint8_t *out;               /* 4-byte aligned */
+	const int32_t *dst_sector;  /* optional [n_sectors] */
+	size_t units_stream_stride; /* bytes between the streams' unit records (a multiple of 16) */
+	size_t out_stream_stride;   /* bytes between the streams' outputs (a multiple of 4) */
+} psxhip_strspu_job_t;
+hipError_t psxhip_strspu_audio_sectors_launch(const psxhip_strspu_job_t *j, int n_streams, void *stream);
 
 #ifdef __cplusplus
 }

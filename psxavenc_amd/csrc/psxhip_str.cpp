@@ -9,6 +9,11 @@
 // concurrently (its own host thread and stream); the host then cuts the finished frames into sectors and interleaves
 // them with the finished audio sectors.  No encoding happens on the host.  No process-global state: everything kept
 // between calls lives in a psxhip_str_ctx_t.
+//
+// Format 8 (STRSPU, "psxhip STRSPU v1") is the same muxer with another audio leg: the sector schedule is a
+// rational share p / q of audio sectors (host_layout.h: strspu_layout), the audio is one SPU-ADPCM chain per channel (5 filters,
+// 4-bit), and an audio sector is a chunk header and 126 SPU blocks placed as the SPUI writer places them (filefmt.c:323-371) --
+// on the device by strspu_kernels.hip, on the host by strspu_place_host below.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -83,6 +88,53 @@ namespace {
 void put_le16(uint8_t* p, unsigned v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); }
 void put_le32(uint8_t* p, unsigned v) { put_le16(p, v & 0xFFFF); put_le16(p + 2, v >> 16); }
 
+int strspu_dummy_of(uint32_t options) { return (options & PSXHIP_STRSPU_NO_LEADING_DUMMY) ? 0 : 1; }      // d: blocks the leading dummy takes
+
+// The 32-byte chunk header of STRSPU audio sector k of K; bytes not set here are zero
+void strspu_chunk_header(uint8_t* hd, const StrspuLayout& x, int frequency, uint32_t options, int k, int K) {
+    const int d = strspu_dummy_of(options);
+    const bool loop = (options & PSXHIP_STRSPU_LOOP) != 0;
+    memset(hd, 0, 32);
+    put_le16(hd + 0x00, 0x0160);
+    put_le16(hd + 0x02, options & PSXHIP_STRSPU_ID_MASK);
+    put_le16(hd + 0x04, 0);
+    put_le16(hd + 0x06, 1);
+    put_le32(hd + 0x08, (unsigned)(k + 1));
+    put_le32(hd + 0x0C, 2016);
+    put_le16(hd + 0x10, (unsigned)x.channels);
+    put_le16(hd + 0x12, (unsigned)x.lane_bytes);
+    put_le32(hd + 0x14, (unsigned)frequency);
+    put_le32(hd + 0x18, k == 0 ? 0u : 28u * (unsigned)(k * x.blocks - d));
+    put_le16(hd + 0x1C, (k == K - 1 ? 1u : 0u) | ((k == 0 && d) ? 2u : 0u) | (loop ? 4u : 0u));
+}
+
+// The host path's block placement: K audio sectors from every channel's U = K B - d encoded blocks (blocks: channel c's at
+// c * U * 16), as strspu_audio_sector_kernel builds them on the device
+void strspu_place_host(const StrspuLayout& x, int frequency, uint32_t options, int K, const uint8_t* blocks, uint8_t* out) {
+    const int d = strspu_dummy_of(options), B = x.blocks;
+    const bool loop = (options & PSXHIP_STRSPU_LOOP) != 0;
+    const size_t U = (size_t)K * B - d;
+    for (int k = 0; k < K; k++) {
+        uint8_t* sec = out + (size_t)k * 2048;
+        strspu_chunk_header(sec, x, frequency, options, k, K);
+        for (int c = 0; c < x.channels; c++) {
+            uint8_t* lane = sec + 0x20 + (size_t)c * x.lane_bytes;
+            for (int b = 0; b < B; b++) {
+                const long long u = (long long)k * B + b - d;
+                if (u < 0) memset(lane + 16 * b, 0, 16);                        // leading silent block, filefmt.c:331-335
+                else memcpy(lane + 16 * b, blocks + ((size_t)c * U + (size_t)u) * 16, 16);
+            }
+            uint8_t* last = lane + 16 * (B - 1);                                // filefmt.c:343-358
+            if (loop) {
+                last[1] = PSX_AUDIO_SPU_LOOP_REPEAT;
+            } else if (k == K - 1) {
+                memset(last, 0, 16);
+                last[1] = PSX_AUDIO_SPU_LOOP_TRAP;
+            }
+        }
+    }
+}
+
 psx_audio_xa_settings_t xa_settings_of(const psxhip_str_settings_t* s) {
     psx_audio_xa_settings_t x;          // args_to_libpsxav_xa_audio, filefmt.c:55-71
     memset(&x, 0, sizeof x);
@@ -95,19 +147,36 @@ psx_audio_xa_settings_t xa_settings_of(const psxhip_str_settings_t* s) {
     return x;
 }
 
-bool settings_ok(const psxhip_str_settings_t* s) {
-    if (!s) return false;
-    if (s->format != FORMAT_STR && s->format != FORMAT_STRCD && s->format != FORMAT_STRV) return false;
+constexpr uint32_t kStrspuOptionBits = PSXHIP_STRSPU_ID_MASK | PSXHIP_STRSPU_LOOP | PSXHIP_STRSPU_NO_LEADING_DUMMY;
+
+// nullptr, or what is wrong with the settings
+const char* settings_error(const psxhip_str_settings_t* s) {
+    static const char* const bad = "psxhip_str: bad settings";
+    if (!s) return bad;
+    if (s->format != FORMAT_STR && s->format != FORMAT_STRCD && s->format != FORMAT_STRV && s->format != FORMAT_STRSPU) return bad;
     if (s->video_codec < 0 || s->video_codec > 2 || s->video_width <= 0 || s->video_height <= 0 ||
         (s->video_width % 16) || (s->video_height % 16))
-        return false;
-    if (s->str_fps_num <= 0 || s->str_fps_den <= 0 || (s->str_cd_speed != 1 && s->str_cd_speed != 2)) return false;
-    if (s->audio_channels < 0 || s->audio_channels > 2) return false;
-    if (s->tail_mode != PSXHIP_STR_TAIL_REFERENCE && s->tail_mode != PSXHIP_STR_TAIL_COMPLETE) return false;
+        return bad;
+    if (s->str_fps_num <= 0 || s->str_fps_den <= 0 || (s->str_cd_speed != 1 && s->str_cd_speed != 2)) return bad;
+    if (s->audio_channels < 0 || s->audio_channels > 2) return bad;
+    if (s->tail_mode != PSXHIP_STR_TAIL_REFERENCE && s->tail_mode != PSXHIP_STR_TAIL_COMPLETE) return bad;
+    if (s->format == FORMAT_STRSPU) {
+        if (s->tail_mode != PSXHIP_STR_TAIL_COMPLETE)
+            return "psxhip_str: format 8 (STRSPU) defines PSXHIP_STR_TAIL_COMPLETE only: the reference has no strspu loop whose tail could be mirrored";
+        if ((uint32_t)s->strspu_options & ~kStrspuOptionBits) return "psxhip_str: unknown bit set in strspu_options";
+        if (s->audio_channels) {
+            if (((uint32_t)s->strspu_options & PSXHIP_STRSPU_ID_MASK) == ((uint32_t)s->str_video_id & 0xFFFFu))
+                return "psxhip_str: the audio chunk id of strspu_options equals str_video_id";
+            if (s->audio_frequency <= 0) return bad;
+            const StrspuLayout x = strspu_layout(s->audio_channels, s->audio_frequency, s->str_cd_speed);
+            if (x.p >= x.q) return "psxhip_str: audio rate too high for this CD speed";
+        }
+        return nullptr;
+    }
     if (s->audio_channels && ((s->audio_frequency != 18900 && s->audio_frequency != 37800) ||
                               (s->audio_bit_depth != 4 && s->audio_bit_depth != 8)))
-        return false;
-    return true;
+        return bad;
+    return nullptr;
 }
 
 // The sector loop of encode_file_str (filefmt.c:450-503) run dry: which frame slice / audio sector lands in which sector
@@ -123,7 +192,11 @@ bool settings_ok(const psxhip_str_settings_t* s) {
 // PSXHIP_STR_TAIL_COMPLETE: every frame is encoded, the stream ends with the last frame's last sector, short audio is padded
 // with silence and only the last audio sector carries EOF.
 int make_plan(const psxhip_str_settings_t* s, int n_frames, int64_t pcm_samples_per_channel, Plan* pl) {
-    if (!settings_ok(s) || n_frames < 0 || pcm_samples_per_channel < 0) {
+    if (const char* why = settings_error(s)) {
+        psxhip_set_error("%s", why);
+        return PSXHIP_EINVAL;
+    }
+    if (n_frames < 0 || pcm_samples_per_channel < 0) {
         psxhip_set_error("psxhip_str: bad settings");
         return PSXHIP_EINVAL;
     }
@@ -133,15 +206,32 @@ int make_plan(const psxhip_str_settings_t* s, int n_frames, int64_t pcm_samples_
     pl->audio_samples = 0;
     const psx_audio_xa_settings_t xa = xa_settings_of(s);
     const int ch = s->audio_channels;
+    const bool spu = s->format == FORMAT_STRSPU && ch;          // (STRSPU without audio is STRV: the branch below, 2048-byte sectors)
+    StrspuLayout sx = {};
     int interleave = 1, sps = 0, vpb = 1;
-    if (ch) {                             // 1/N audio, (N-1)/N video, filefmt.c:399-403
-        interleave = (int)psx_audio_xa_get_sector_interleave(xa) * s->str_cd_speed;
-        sps = (int)psx_audio_xa_get_samples_per_sector(xa);
-        vpb = interleave - 1;
+    if (spu) {
+        // p / q of the sectors are audio: the budgets are mdec.c:768-775's with (q - p) / q of 75 x speed sectors a second for video
+        // -- for p / q = 1 / N the numbers of filefmt.c:428-429
+        sx = strspu_layout(ch, s->audio_frequency, s->str_cd_speed);
+        sps = sx.samples_per_sector;
+        const int64_t base = 75ll * s->str_cd_speed * (sx.q - sx.p) * s->str_fps_den, den = sx.q * s->str_fps_num;
+        if (base > 0x7FFFFFFFll || den > 0x7FFFFFFFll) {
+            psxhip_set_error("psxhip_str: frame rate and audio rate do not fit the budget arithmetic (base %lld, den %lld)", (long long)base, (long long)den);
+            return PSXHIP_EINVAL;
+        }
+        pl->base = (int)base;
+        pl->den = (int)den;
+        interleave = sx.q % sx.p == 0 ? (int)(sx.q / sx.p) : 0;
+    } else {
+        if (ch) {                             // 1/N audio, (N-1)/N video, filefmt.c:399-403
+            interleave = (int)psx_audio_xa_get_sector_interleave(xa) * s->str_cd_speed;
+            sps = (int)psx_audio_xa_get_samples_per_sector(xa);
+            vpb = interleave - 1;
+        }
+        pl->base = 75 * s->str_cd_speed * vpb * s->str_fps_den;
+        pl->den = interleave * s->str_fps_num;
     }
-    pl->base = 75 * s->str_cd_speed * vpb * s->str_fps_den;
-    pl->den = interleave * s->str_fps_num;
-    pl->pub.sector_size = (int32_t)psx_audio_xa_get_buffer_size_per_sector(xa);
+    pl->pub.sector_size = s->format == FORMAT_STRSPU ? 2048 : (int32_t)psx_audio_xa_get_buffer_size_per_sector(xa);
     pl->pub.interleave = interleave;
     pl->pub.audio_samples_per_sector = sps;
     if (pl->base / pl->den < 1) {
@@ -157,7 +247,8 @@ int make_plan(const psxhip_str_settings_t* s, int n_frames, int64_t pcm_samples_
     long long V = n_frames;                                    // frames the decoder still holds
     long long A = ch ? pcm_samples_per_channel * ch : 0;       // interleaved samples the decoder still holds
     bool eoi = false;
-    int offset = 0, max_size = 0, num = 0, frame = -1, audio_sectors = 0, video_sectors = 0, max_budget = 0;
+    int offset = 0, max_size = 0, frame = -1, audio_sectors = 0, video_sectors = 0, max_budget = 0;
+    long long num = 0;
     // complete mode: the audio slots of the whole stream are filled (silence when the PCM runs out)
     for (long long n = 0;; n++) {
         if (reference) {
@@ -173,6 +264,7 @@ int make_plan(const psxhip_str_settings_t* s, int n_frames, int64_t pcm_samples_
         }
         bool video;                                            // filefmt.c:454-461
         if (!sps) video = true;
+        else if (spu) video = strspu_audio_before(sx, s->trailing_audio != 0, n + 1) == strspu_audio_before(sx, s->trailing_audio != 0, n);
         else if (s->trailing_audio) video = (n % interleave) < vpb;
         else video = (n % interleave) > 0;
         Sector sec;
@@ -182,8 +274,8 @@ int make_plan(const psxhip_str_settings_t* s, int n_frames, int64_t pcm_samples_
             if (offset >= max_size && V <= 0) break;
             while (offset >= max_size) {                       // encode_sector_str moves on to the next frame, mdec.c:768-780
                 frame++;
-                num += pl->base;
-                max_size = num / pl->den * 2016;
+                num += pl->base;                               // (base + den - 1 < 2^32: no overflow in 64 bits)
+                max_size = (int)(num / pl->den * 2016);
                 num %= pl->den;
                 offset = 0;
                 pl->budgets.push_back(max_size);
@@ -218,6 +310,13 @@ int make_plan(const psxhip_str_settings_t* s, int n_frames, int64_t pcm_samples_
     if (!reference && audio_sectors > 0)                       // only the last audio sector carries EOF
         for (size_t i = pl->sectors.size(); i-- > 0;)
             if (pl->sectors[i].frame == -1) { pl->sectors[i].eof = 1; break; }
+    // STRSPU: the K audio sectors hold K B blocks per channel, the first of them the dummy block: the chains encode U = K B - d units,
+    // the PCM is fitted to 28 U samples (silence behind a shorter one)
+    if (spu && 28ll * audio_sectors * sx.blocks > 0x7FFFFFFFll) {          // (a chain's sample limit is an int)
+        psxhip_set_error("psxhip_str: stream too long");
+        return PSXHIP_EINVAL;
+    }
+    if (spu) pl->audio_samples = audio_sectors ? 28ll * ((long long)audio_sectors * sx.blocks - strspu_dummy_of((uint32_t)s->strspu_options)) : 0;
     pl->pub.n_sectors = (int32_t)pl->sectors.size();
     pl->pub.n_video_sectors = video_sectors;
     pl->pub.n_audio_sectors = (int32_t)pl->sectors.size() - video_sectors;
@@ -311,7 +410,10 @@ extern "C" int psxhip_str_frame_budgets(const psxhip_str_settings_t* settings, i
     if (!budgets || first_frame < 0 || n_frames < 0) return PSXHIP_EINVAL;
     // the budget sequence does not depend on how the stream ends: plan all frames in the complete mode (mdec.c:768-775)
     psxhip_str_settings_t s2;
-    if (!settings) return PSXHIP_EINVAL;
+    if (const char* why = settings_error(settings)) {          // (a tail the format does not define is refused here too)
+        psxhip_set_error("%s", why);
+        return PSXHIP_EINVAL;
+    }
     s2 = *settings;
     s2.tail_mode = PSXHIP_STR_TAIL_COMPLETE;
     Plan pl;
@@ -468,7 +570,24 @@ extern "C" int psxhip_str_encode_host(psxhip_str_ctx_t* c, const psxhip_str_sett
     int na = 0;
     for (const Sector& sc : pl.sectors) na += sc.frame == -1;
     int rc_audio = PSXHIP_OK;
-    if (na > 0) {
+    if (na > 0 && s->format == FORMAT_STRSPU) {
+        // STRSPU: every channel is one SPU chain over its samples fitted to 28 U (cut, or completed with silence), all channels in one
+        // batched call; the host only places the blocks
+        const StrspuLayout sx = strspu_layout(ch, s->audio_frequency, s->str_cd_speed);
+        const int64_t fit = pl.audio_samples;                      // 28 U, an int's worth (make_plan)
+        const int64_t have = pcm_samples_per_channel < fit ? pcm_samples_per_channel : fit;
+        std::vector<int16_t> planar((size_t)fit * ch, 0);
+        for (int k = 0; k < ch; k++)
+            for (int64_t i = 0; i < have; i++) planar[(size_t)k * fit + i] = pcm[(size_t)i * ch + k];
+        std::vector<uint8_t> blocks((size_t)(fit / 28) * 16 * ch);
+        psxhip_adpcm_state_t st[2] = {{0, 0}, {0, 0}};
+        rc_audio = psxhip_spu_encode_streams_host(device, planar.data(), ch, fit, 1, (int)fit, st, blocks.data(), fit / 28 * 16);
+        if (rc_audio >= 0) {
+            xa_out.resize((size_t)na * ssz);
+            strspu_place_host(sx, s->audio_frequency, (uint32_t)s->strspu_options, na, blocks.data(), xa_out.data());
+            rc_audio = PSXHIP_OK;
+        }
+    } else if (na > 0) {
         // The XA encoder is handed pl.audio_samples per channel (the sum of the sector loop's samples_length, filefmt.c:476-479).
         // A short last sector is completed from zeros: what lies past the end of the PCM data is zero in the reference's
         // decoder buffer too (decoding.c:395-398,521-527), which is what its stereo tail over-reads.  The complete
@@ -577,7 +696,8 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
         std::vector<int32_t> budgets((size_t)nf * n_streams);
         for (int i = 0; i < n_streams; i++)
             for (int f = 0; f < nf; f++) budgets[(size_t)i * nf + f] = pl.budgets[(size_t)f];
-        const size_t units_per_stream = (size_t)d.na * xa_layout(s->format == FORMAT_STRCD, s->audio_channels == 2, s->audio_bit_depth).units_per_sector;
+        // (STRSPU: 126 SPU blocks per audio sector; the records are the smaller of the two kinds, so the size below covers them)
+        const size_t units_per_stream = (size_t)d.na * (s->format == FORMAT_STRSPU ? 126 : xa_layout(s->format == FORMAT_STRCD, s->audio_channels == 2, s->audio_bit_depth).units_per_sector);
         auto up = [](DeviceBuffer& dst, const void* src, size_t bytes) -> int {
             const int rc = dst.reserve(bytes ? bytes : 4);
             if (rc) return rc;
@@ -671,9 +791,12 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     // ---- audio: the streams' XA tracks as chains of one session on the handle's own stream, behind the caller's inputs; the
     //      host drives the verify passes (the call is synchronous), the video leg above runs meanwhile
     if (na) {
-        const int ch = s->audio_channels, bits = s->audio_bit_depth;
+        // STRSPU: one SPU chain per channel (5 filters, 4-bit), U = K B - d units each in a stream's K x 126 records of 16 bytes
+        const bool spu = s->format == FORMAT_STRSPU;
+        const int ch = s->audio_channels, bits = spu ? 4 : s->audio_bit_depth, filters = spu ? 5 : 4;
         const XaLayout xa = xa_layout(s->format == FORMAT_STRCD, ch == 2, bits);
-        const int units_per_stream = na * xa.units_per_sector, units_per_chain = units_per_stream / ch;
+        const int units_per_stream = na * (spu ? 126 : xa.units_per_sector);
+        const int units_per_chain = units_per_stream / ch - (spu ? strspu_dummy_of((uint32_t)s->strspu_options) : 0);
         const int64_t need = pl.audio_samples;                                   // per channel, over the whole stream
         const int limit = (int)(pcm_samples_per_channel < need ? pcm_samples_per_channel : need);      // past it the encoder reads zeros (decoding.c:521-527)
         if (n_streams > 1 && pcm_stream_stride < (int64_t)limit * ch) {
@@ -692,10 +815,11 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             std::vector<psxhip_adpcm_chain_t> chains((size_t)n_chains);
             std::vector<int32_t> base((size_t)n_chains);
             fill_interleaved_chains(chains.data(), base.data(), n_streams, ch, pcm_stream_stride, limit, units_per_stream);
+            for (psxhip_adpcm_chain_t& chain : chains) chain.n_units = units_per_chain;
             if (chunked) {
                 int chunk_units = 0, warmup_units = 0;
                 psxhip_adpcm_pick_chunking((long long)units_per_chain * n_chains, 5, device, &chunk_units, &warmup_units);
-                const int rc = psxhip_adpcm_session_create(&d.session, device, d_pcm, chains.data(), base.data(), nullptr, n_chains, 4, bits,
+                const int rc = psxhip_adpcm_session_create(&d.session, device, d_pcm, chains.data(), base.data(), nullptr, n_chains, filters, bits,
                                                            d.buf.units.as<uint8_t>(), chunk_units, warmup_units, d.astream);
                 if (rc) return fail(rc);
             } else {
@@ -723,13 +847,17 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
             if (rc < 0) return fail(rc);
         } else {
             HIP_TRY(hipMemsetAsync(d.tab.states.p, 0, (size_t)n_chains * sizeof(psxhip_adpcm_state_t), d.astream), PSXHIP_EDEVICE);
-            rc = psxhip_adpcm_encode_chains_device(device, d_pcm, d.tab.chains.as<const psxhip_adpcm_chain_t>(), d.tab.base.as<const int32_t>(), n_chains, 4,
+            rc = psxhip_adpcm_encode_chains_device(device, d_pcm, d.tab.chains.as<const psxhip_adpcm_chain_t>(), d.tab.base.as<const int32_t>(), n_chains, filters,
                                                    bits, d.tab.states.as<psxhip_adpcm_state_t>(), d.buf.units.as<uint8_t>(), d.astream);
             if (rc) return fail(rc);
         }
-        rc = psxhip_xa_assemble_scatter(device, d.buf.units.as<const uint8_t>(), na, s->format == FORMAT_STRCD ? 1 : 0, ch == 2, s->audio_frequency, bits,
-                                        s->audio_xa_file, s->audio_xa_channel, 0, d.buf.eof.as<const uint8_t>(), 0u, d_out, d.buf.adst.as<const int32_t>(),
-                                        n_streams, (size_t)units_per_stream * xa.record_bytes, out_stream_stride, d.astream);
+        if (spu)
+            rc = psxhip_strspu_audio_sectors_device(device, d.buf.units.as<const uint8_t>(), na, ch, s->audio_frequency, (uint32_t)s->strspu_options, n_streams,
+                                                    (size_t)units_per_stream * xa.record_bytes, d_out, d.buf.adst.as<const int32_t>(), out_stream_stride, d.astream);
+        else
+            rc = psxhip_xa_assemble_scatter(device, d.buf.units.as<const uint8_t>(), na, s->format == FORMAT_STRCD ? 1 : 0, ch == 2, s->audio_frequency, bits,
+                                            s->audio_xa_file, s->audio_xa_channel, 0, d.buf.eof.as<const uint8_t>(), 0u, d_out, d.buf.adst.as<const int32_t>(),
+                                            n_streams, (size_t)units_per_stream * xa.record_bytes, out_stream_stride, d.astream);
         if (rc) return fail(rc);
         HIP_TRY(hipEventRecord(d.ev_audio, d.astream), PSXHIP_EDEVICE);
         HIP_TRY(hipStreamWaitEvent(S, d.ev_audio, 0), PSXHIP_EDEVICE);
@@ -770,3 +898,40 @@ extern "C" int psxhip_str_encode_device(psxhip_str_ctx_t* c, const psxhip_str_se
     if (plan_out) plan_out->quant_scale_sum = qsum;
     return PSXHIP_OK;
 }
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// The STRSPU audio sector builder on its own: unit records in HBM -> audio sectors in their slots (strspu_kernels.hip)
+extern "C" int psxhip_strspu_audio_sectors_device(int device, const uint8_t* d_units, int n_sectors, int channels, int frequency, uint32_t options,
+                                                  int n_streams, size_t units_stream_stride, uint8_t* d_out, const int32_t* d_dst_sector,
+                                                  size_t out_stream_stride, void* stream) {
+    if (!d_units || !d_out || n_sectors < 0 || n_sectors > 0x7FFFFFFF / 126 || n_streams < 1 || n_streams > 65535 || (channels != 1 && channels != 2) ||
+        frequency <= 0 || (options & ~kStrspuOptionBits) || ((uintptr_t)d_units & 15) || (units_stream_stride & 15) || ((uintptr_t)d_out & 3) ||
+        (out_stream_stride & 3) || ((uintptr_t)d_dst_sector & 3)) {
+        psxhip_set_error("psxhip_strspu_audio_sectors_device: bad argument (d_units and its stride 16-byte aligned, d_out and its stride 4-byte aligned, "
+                         "1 or 2 channels, no unknown option bit)");
+        return PSXHIP_EINVAL;
+    }
+    if (n_streams > 1 && (units_stream_stride < (size_t)n_sectors * 126 * PSXHIP_ADPCM_RECORD_BYTES_4BIT || (!d_dst_sector && out_stream_stride < (size_t)n_sectors * 2048))) {
+        psxhip_set_error("psxhip_strspu_audio_sectors_device: a stream stride smaller than a stream");
+        return PSXHIP_EINVAL;
+    }
+    const int rc = psxhip_ensure_device(device);
+    if (rc) return rc;
+    if (n_sectors == 0) return PSXHIP_OK;
+    psxhip_strspu_job_t job;
+    memset(&job, 0, sizeof job);
+    job.units = d_units;
+    job.n_sectors = n_sectors;
+    job.channels = channels;
+    job.frequency = frequency;
+    job.options = options;
+    job.out = d_out;
+    job.dst_sector = d_dst_sector;
+    job.units_stream_stride = units_stream_stride;
+    job.out_stream_stride = out_stream_stride;
+    HIP_TRY(psxhip_strspu_audio_sectors_launch(&job, n_streams, stream), PSXHIP_EDEVICE);
+    return PSXHIP_OK;
+}
+
+extern "C" const char* psxhip_strspu_kernel_rev(void) { return PSXHIP_STRSPU_KERNEL_REV; }

@@ -1,4 +1,4 @@
-"""STR / STRCD / STRV muxer -- Python mirror of psxhip_str_* (include/psxav_hip.h).
+"""STR / STRCD / STRV / STRSPU muxer -- Python mirror of psxhip_str_* (include/psxav_hip.h).
 
 Reference surface: ``encode_file_str`` (psxavenc/filefmt.c:391-520) around ``encode_sector_str``
 (psxavenc/mdec.c:757-836) and ``psx_audio_xa_encode`` (libpsxav/adpcm.c:293-332)."""
@@ -9,6 +9,8 @@ import numpy as np
 from . import _lib
 
 FORMAT_STR, FORMAT_STRCD, FORMAT_STRV = 6, 7, 9
+FORMAT_STRSPU = 8                         # .str video + SPU-ADPCM audio chunks in 2048-byte sectors ("psxhip STRSPU v1")
+STRSPU_LOOP, STRSPU_NO_LEADING_DUMMY = 1 << 16, 1 << 17      # PSXHIP_STRSPU_*: bits of strspu_options above the audio chunk id
 TAIL_REFERENCE, TAIL_COMPLETE = 0, 1      # PSXHIP_STR_TAIL_*: how the stream ends (see include/psxav_hip.h)
 PLENTY_OF_AUDIO = 1 << 40                 # plan(): "the audio never ends before the video does"
 
@@ -18,7 +20,7 @@ class StrSettings(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "format", "video_codec", "video_width", "video_height", "str_fps_num", "str_fps_den", "str_cd_speed",
         "str_video_id", "trailing_audio", "audio_channels", "audio_frequency", "audio_bit_depth", "audio_xa_file",
-        "audio_xa_channel", "tail_mode", "reserved")]
+        "audio_xa_channel", "tail_mode", "strspu_options")]
 
 
 class StrPlan(C.Structure):
@@ -28,10 +30,14 @@ class StrPlan(C.Structure):
 
 
 def settings(fmt=FORMAT_STRCD, codec=0, width=320, height=240, fps_num=15, fps_den=1, cd_speed=2, video_id=0x8001,
-             trailing_audio=False, channels=2, frequency=37800, bits=4, xa_file=1, xa_channel=0, tail=TAIL_REFERENCE):
-    """defaults = config 'strcd v2' (args.c:149-187 + SURVEY 3.2); tail = the reference's end-of-input model"""
+             trailing_audio=False, channels=2, frequency=37800, bits=4, xa_file=1, xa_channel=0, tail=TAIL_REFERENCE,
+             audio_id=0x0001, spu_loop=False, spu_no_leading_dummy=False):
+    """defaults = config 'strcd v2' (args.c:149-187 + SURVEY 3.2); tail = the reference's end-of-input model.
+    audio_id / spu_loop / spu_no_leading_dummy: format 8's strspu_options (the other formats ignore them); format 8 wants
+    tail=TAIL_COMPLETE"""
+    options = (int(audio_id) & 0xFFFFFFFF) | (STRSPU_LOOP if spu_loop else 0) | (STRSPU_NO_LEADING_DUMMY if spu_no_leading_dummy else 0)
     return StrSettings(fmt, codec, width, height, fps_num, fps_den, cd_speed, video_id, int(trailing_audio), channels,
-                       frequency, bits, xa_file, xa_channel, tail, 0)
+                       frequency, bits, xa_file, xa_channel, tail, options - (1 << 32) if options >> 31 else options)
 
 
 def _bind():
@@ -45,7 +51,39 @@ def _bind():
                                          C.c_void_p, C.c_size_t, C.POINTER(StrPlan)]
     L.psxhip_str_encode_device.argtypes = [C.c_void_p, C.POINTER(StrSettings), C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p,
                                            C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(StrPlan), C.c_void_p]
+    L.psxhip_strspu_audio_sectors_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_size_t, C.c_void_p,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p]
+    L.psxhip_strspu_kernel_rev.restype = C.c_char_p
     return L
+
+
+def strspu_kernel_rev():
+    return _bind().psxhip_strspu_kernel_rev().decode()
+
+
+def strspu_audio_sectors_device(d_units, n_sectors, channels, frequency, options=0x0001, d_out=None, d_dst_sector=None, stream=None):
+    """psxhip_strspu_audio_sectors_device: the audio sector builder of format 8 on its own.  d_units: uint8 CUDA tensor
+    (S, n_sectors * 126, 16) (or (n_sectors * 126, 16) for one stream), unit u of channel c at record u * channels + c; options:
+    audio chunk id | STRSPU_*.  d_dst_sector: optional int32 CUDA tensor (n_sectors,), the slot of every sector in d_out (then
+    d_out, (S, slots, 2048), must be given); else the output is dense (S, n_sectors, 2048).  Asynchronous; returns d_out."""
+    import torch
+    if d_units.dim() == 2:
+        d_units = d_units.unsqueeze(0)
+    assert d_units.is_cuda and d_units.dtype == torch.uint8 and d_units.is_contiguous() and tuple(d_units.shape[1:]) == (n_sectors * 126, 16)
+    n_streams = d_units.shape[0]
+    if d_out is None:
+        assert d_dst_sector is None
+        d_out = torch.zeros((n_streams, n_sectors, 2048), dtype=torch.uint8, device=d_units.device)
+    assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.dim() == 3 and d_out.shape[0] == n_streams and d_out.shape[2] == 2048
+    if d_dst_sector is not None:
+        assert d_dst_sector.is_cuda and d_dst_sector.dtype == torch.int32 and d_dst_sector.is_contiguous() and d_dst_sector.numel() == n_sectors
+    else:
+        assert d_out.shape[1] >= n_sectors
+    st = stream if stream is not None else torch.cuda.current_stream(d_units.device)
+    _lib.check(_bind().psxhip_strspu_audio_sectors_device(
+        d_units.device.index or 0, d_units.data_ptr(), n_sectors, channels, frequency, options, n_streams, d_units.stride(0), d_out.data_ptr(),
+        d_dst_sector.data_ptr() if d_dst_sector is not None else None, d_out.stride(0), st.cuda_stream))
+    return d_out
 
 
 def plan(s, n_frames, pcm_samples_per_channel=PLENTY_OF_AUDIO):
