@@ -28,6 +28,11 @@ static inline XaLayout xa_layout(int format, int stereo, int bits) {
     return x;
 }
 
+// sectors from one sector of an XA channel to its next at 1x speed (filefmt.c:399-403): 2 stereo, 4 mono; x 2 at 18900 Hz, x 2 at 4 bits
+static inline int xa_sector_interleave(int stereo, int frequency, int bits) {
+    return (stereo ? 2 : 4) * (frequency == 18900 ? 2 : 1) * (bits == 4 ? 2 : 1);
+}
+
 // format 6 (STR), 7 (STRCD), 9 (STRV): bytes per sector, where the XA subheader lies (-1: none) and the chunk header (mdec.c:822-829)
 static inline bool str_sector_geometry(int format, int* sector_size, int* sub_at, int* hdr_at) {
     switch (format) {

@@ -8,11 +8,11 @@
 
 #include <new>
 
-#include "../../include/psxav_audio.h"
 #include "device_buffer.h"
 #include "host_layout.h"
 #include "psxhip_internal.h"
 #include "psxhip_str_demux_internal.h"
+#include "str_plan.h"
 
 struct psxhip_str_reader {
     int device = 0;
@@ -150,18 +150,8 @@ extern "C" int psxhip_str_read_host(psxhip_str_reader_t* reader, const psxhip_st
         return PSXHIP_EINVAL;
     }
     // the widest frame the rate allows: the budgets of mdec.c:768-775 never pass ceil(base / den) chunks (filefmt.c:399-403,431-432)
-    long long interleave = 1, vpb = 1;
-    if (ch) {
-        psx_audio_xa_settings_t xa;
-        memset(&xa, 0, sizeof xa);
-        xa.bits_per_sample = s->audio_bit_depth;
-        xa.frequency = s->audio_frequency;
-        xa.stereo = ch == 2;
-        interleave = (long long)psx_audio_xa_get_sector_interleave(xa) * s->str_cd_speed;
-        vpb = interleave - 1;
-    }
-    const long long base = 75ll * s->str_cd_speed * vpb * s->str_fps_den, den = interleave * s->str_fps_num;
-    const long long chunks = (base + den - 1) / den;
+    const StrRates rates = str_rates(s);
+    const long long chunks = (long long)((rates.base + rates.den - 1) / rates.den);
     if (chunks < 1 || chunks > 65536) {
         psxhip_set_error("psxhip_str_read_host: the frame rate and CD speed give a frame %lld chunks", chunks);
         return PSXHIP_EINVAL;

@@ -21,6 +21,7 @@ int main() {
                 const XaLayout x = xa_layout(format, stereo, bits);
                 printf("xa %d %d %d : %d %d %d %d %d %d\n", format, stereo, bits, x.channels, x.units_per_group, x.units_per_sector, x.sector_bytes,
                        x.samples_per_sector, x.record_bytes);
+                printf("xa_interleave %d %d %d : %d %d\n", format, stereo, bits, xa_sector_interleave(stereo, 18900, bits), xa_sector_interleave(stereo, 37800, bits));
             }
     for (int format : {6, 7, 9, 8}) {
         int size = -7, sub = -7, hdr = -7;                      // an unknown format leaves them alone

@@ -41,7 +41,7 @@ def _threshold(n_chains):
 
 
 def _units_per_chain(s, n_frames, per_ch):
-    """units every ADPCM chain of the call encodes (psxhip_str.cpp: na * units_per_sector / channels), from the plan alone:
+    """units every ADPCM chain of the call encodes (psxhip_str.cpp, rebuild_shape: units_per_chain = na * units_per_sector / channels), from the plan alone:
     a sector holds 18 sound groups of 8 (4-bit) or 4 (8-bit) units, shared by the channels"""
     from psxavenc_amd import strmux
     rows = strmux.plan_sectors(s, n_frames, per_ch)
@@ -169,7 +169,7 @@ def test_audio_layout_matrix_both_adpcm_routes(case):
     for which, n_frames in (("long", long_n), ("short", short_n)):
         n = _plenty(s, n_frames)
         units, na = _units_per_chain(s, n_frames, n)
-        # the two calls take the two routes (psxhip_str.cpp: chunked = units_per_chain >= threshold), whatever the threshold becomes
+        # the two calls take the two routes (psxhip_str.cpp, audio_leg: chunked = units_per_chain >= threshold), whatever the threshold becomes
         if which == "long":
             assert units >= thr, (units, thr)
         else:
@@ -329,8 +329,8 @@ def test_complete_tail_three_streams_single_batch_and_batch_list(kw):
 
 # ---------------------------------------------------------------------------------------------------------------- 4. the cache
 def test_handle_cache_shape_sequence_same_pointers_new_contents_and_after_an_error():
-    """one handle through everything that decides what it keeps between calls (psxhip_str.cpp: settings, frame count, PCM length,
-    d_pcm, PCM stride, chunked or serial): a sequence of shapes, the same device pointers with new contents on both ADPCM routes, and
+    """one handle through everything that decides what it keeps between calls (psxhip_str.cpp: settings, frame count, PCM length and stream count
+    rebuild the shape, rebuild_shape; d_pcm, PCM stride, chunked or serial the session or chain tables, audio_leg): a sequence of shapes, the same device pointers with new contents on both ADPCM routes, and
     a call after PSXHIP_ENOFIT -- each result against the reference loop"""
     import torch
     from psxavenc_amd import _lib, strmux

@@ -40,7 +40,7 @@ def ints(text):
 def test_xa_layout_is_the_formats(lines):
     """A sector is 18 sound groups of 128 bytes: 16 bytes of headers and 112 of codes, 28 codes to a unit; 2336 bytes with the
     subheader in front (XA), 2352 with sync and header too (XACD).  A unit record is an SPU block (2 + 14 bytes) for 4-bit codes and
-    4 + 28 bytes for 8-bit ones (include/psxav_hip.h)."""
+    4 + 28 bytes for 8-bit ones (include/psxav_hip.h).  The sector interleave is what the playback rate makes of that (filefmt.c:399-403)."""
     seen = set()
     for line in lines["xa"]:
         (fmt, stereo, bits), got = (ints(part) for part in line.split(":"))
@@ -51,6 +51,14 @@ def test_xa_layout_is_the_formats(lines):
         assert want[4] == {4: 4032, 8: 2016}[bits]
         seen.add((fmt, stereo, bits))
     assert seen == {(f, s, b) for f in (0, 1) for s in (0, 1) for b in (4, 8)}
+    # the sector interleave: at 1x the drive reads 75 sectors a second, a channel plays 18900 or 37800 samples a second out of each of
+    # its sectors -- one sector in every 75 x (samples per channel per sector) / rate is that channel's
+    for line in lines["xa_interleave"]:
+        (fmt, stereo, bits), got = (ints(part) for part in line.split(":"))
+        per_channel = 18 * (112 * 8 // bits) // (2 if stereo else 1)
+        assert got == [75 * per_channel // 18900, 75 * per_channel // 37800] and 75 * per_channel % 37800 == 0, line
+        seen.discard((fmt, stereo, bits))
+    assert not seen
 
 
 def test_str_sector_geometry_matches_the_python_tables(lines):
