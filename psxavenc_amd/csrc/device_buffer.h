@@ -38,3 +38,51 @@ struct __attribute__((visibility("hidden"))) DeviceBuffer {      // (not part of
     }
     template <class T> T* as() const { return (T*)p; }
 };
+
+// The other things a handle owns, by the same rules (move-only, not part of the library's surface, never static): a page-locked host
+// block, a stream, an event
+template <class T, hipError_t (*Destroy)(T)>
+struct __attribute__((visibility("hidden"))) HipOwned {
+    T h = nullptr;
+
+    HipOwned() = default;
+    HipOwned(const HipOwned&) = delete;
+    HipOwned& operator=(const HipOwned&) = delete;
+    HipOwned(HipOwned&& o) noexcept : h(o.h) { o.h = nullptr; }
+    HipOwned& operator=(HipOwned&& o) noexcept {
+        if (this != &o) {
+            release();
+            h = o.h;
+            o.h = nullptr;
+        }
+        return *this;
+    }
+    ~HipOwned() { release(); }
+
+    void release() {
+        if (h) (void)Destroy(h);
+        h = nullptr;
+    }
+    operator T() const { return h; }
+};
+struct __attribute__((visibility("hidden"))) PinnedBlock : HipOwned<void*, hipHostFree> {
+    // a new block of `bytes` (the old one is gone): hipHostMalloc's flags
+    int alloc(size_t bytes, unsigned flags) {
+        release();
+        HIP_TRY(hipHostMalloc(&h, bytes, flags), PSXHIP_ENOMEM);
+        return PSXHIP_OK;
+    }
+    uint8_t* bytes() const { return (uint8_t*)h; }
+};
+struct __attribute__((visibility("hidden"))) Stream : HipOwned<hipStream_t, hipStreamDestroy> {
+    int ensure() {          // a non-blocking stream, created at first use
+        if (!h) HIP_TRY(hipStreamCreateWithFlags(&h, hipStreamNonBlocking), PSXHIP_EDEVICE);
+        return PSXHIP_OK;
+    }
+};
+struct __attribute__((visibility("hidden"))) Event : HipOwned<hipEvent_t, hipEventDestroy> {
+    int ensure() {          // an event without timing, created at first use
+        if (!h) HIP_TRY(hipEventCreateWithFlags(&h, hipEventDisableTiming), PSXHIP_EDEVICE);
+        return PSXHIP_OK;
+    }
+};

@@ -50,15 +50,6 @@
 
 namespace {
 
-constexpr int kSplitWaves = 16, kSplitThreads = kSplitWaves * 64;
-constexpr int kSplitRound = 16;              // scales evaluated per round (eight in a first round that has a low hint)
-constexpr int kSplitRounds = 5;              // 8 + 4 x 16 >= 63
-// a macroblock's stream is at most 6 x (DC code <= 24 bits + 63 escapes + end of block) bits, + the end-of-frame code, + slack
-constexpr int kSplitMbMaxBits = 6 * (24 + 63 * 22 + 2);
-constexpr int kSplitWbufWords = (kSplitMbMaxBits + 10 + 31) / 32 + 2;
-static_assert(kSplitWbufWords * 4 >= 6 * kTileStride * 2, "a wavefront's transpose tile fits its stream buffer");
-constexpr unsigned long long kSplitPatience = 20000000ull;    // ticks of the 100 MHz wall clock a rendezvous waits: 0.2 s (default)
-
 struct SplitJob {
     const uint8_t* frames;
     uint8_t* out;
@@ -108,23 +99,6 @@ __device__ __forceinline__ void split_put_bits(uint32_t* words, uint32_t pos, in
     const uint32_t hi = top >> sh, lo = __builtin_amdgcn_alignbit(top, 0u, sh);
     __hip_atomic_fetch_or(&words[w], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (lo) __hip_atomic_fetch_or(&words[w + 1], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__host__ __device__ inline int split_dc_chunks(int nmb) { return 2 * ((nmb + 511) >> 9) + ((4 * nmb + 511) >> 9); }
-__host__ __device__ inline size_t split_lds_bytes(int codec, int M, int nmb) {
-    size_t b = 0;
-    b += 96 * 4;                                        // scalars
-    b += (BS_LUT_SIZE * 2 + 15) & ~15;                  // ac_len16
-    b += (BS_LUT_SIZE * 4 + 15) & ~15;                  // ac_code
-    b += (size_t)M * 6 * 64 * 2;                        // coefficients, scan order
-    b += (size_t)M * kSplitRound * 4;                   // macroblock bits per scale of the round
-    b += (size_t)M * 8 * 2;                             // quantised DC of the segment's blocks
-    b += (size_t)kSplitWaves * kSplitWbufWords * 4;     // per-wavefront stream buffers (the transpose tiles alias them)
-    if (codec != 0) {
-        b += ((size_t)nmb * 6 * 2 + 15) & ~15;          // the frame's DC terms / deltas
-        b += (size_t)split_dc_chunks(nmb) * 16;         // chain scan
-    }
-    return (b + 15) & ~(size_t)15;
 }
 
 template <int CODEC>
@@ -640,33 +614,6 @@ __global__ __launch_bounds__(kSplitThreads, 8) void mdec_split_kernel(const Spli
 }
 
 }  // namespace
-
-extern "C" int psxhip_mdec_split_geometry(int codec, int width, int height, int max_frame_size, int n_frames, int n_cu, psxhip_mdec_split_geo_t* g) {
-    const int nx = width / 16, ny = height / 16, nmb = nx * ny;
-    memset(g, 0, sizeof *g);
-    if (nmb <= 0 || n_frames <= 0 || n_cu <= 0) return 0;
-    // M: every group of every frame resident at once when that can be had (segments x frames <= CUs), and never more segments
-    // than CUs per frame -- a frame's groups wait for each other
-    int M = 2;
-    while (M < 16 && (long long)((nmb + M - 1) / M) * n_frames > n_cu) M *= 2;
-    static const int forced_m = [] { const char* e = getenv("PSXHIP_MDEC_SPLIT_M"); return e ? atoi(e) : 0; }();     // experiments only; read once
-    if (forced_m == 1 || forced_m == 2 || forced_m == 4 || forced_m == 8 || forced_m == 16) M = forced_m;
-    const int segs = (nmb + M - 1) / M;
-    if (segs > n_cu) return 0;                                      // (more than 16 x CUs macroblocks: the frame kernel takes it)
-    g->seg_mbs = M;
-    g->segs = segs;
-    g->img_words = (max_frame_size + 3) / 4 + 2;
-    // the workspace's layout depends on the context's constants only (frame size, largest budget), not on M: launches of one
-    // context with different M share it
-    size_t o = 64;
-    g->ws_slots = o;    o += (size_t)kSplitRounds * nmb * kSplitRound * 8;
-    g->ws_dcq = o;      o += ((size_t)nmb * 3 * 4 + 15) & ~(size_t)15;
-    g->ws_img = o;      o += (size_t)g->img_words * 4;
-    g->ws_done = o;     o += ((size_t)nmb * 4 + 15) & ~(size_t)15;
-    g->ws_stride = (o + 127) & ~(size_t)127;
-    g->lds_bytes = split_lds_bytes(codec, M, nmb);
-    return g->lds_bytes <= 64 * 1024 ? 1 : 0;
-}
 
 extern "C" hipError_t psxhip_mdec_split_launch(const psxhip_mdec_split_t* a) {
     SplitJob job;

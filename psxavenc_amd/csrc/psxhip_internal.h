@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/psxav_hip.h"
+#include "mdec_plan.h"
 
 /* bumped with every change to the MDEC kernel: bench.py keys the committed PMC summaries on it (profiles/pmc_index.json) */
 #define PSXHIP_MDEC_KERNEL_REV "mdec-k3.9"
@@ -39,15 +40,10 @@ typedef struct {
 	unsigned long long *d_stats;    /* optional [PSXHIP_MDEC_STATS] diagnostics */
 	int trust_mode;                 /* 0 = the trust policy; experiments: 1 = foreign hints always trusted, 2 = never */
 	const uint32_t *d_order;        /* psxhip_mdec_pass_table() for this geometry, in device memory */
+	int trips, it_step;             /* a pass's iterations and their visiting stride (mdec_launch_policy) */
 } psxhip_mdec_launch_t;
 
-/* one frame across many workgroups (mdec_split.inc): launches of a few frames -- the drop-in's one frame per call most of all */
-typedef struct {
-	int seg_mbs, segs;                  /* macroblocks per workgroup (1, 2, 4, 8, 16), workgroups per frame */
-	int img_words;
-	size_t ws_stride, ws_slots, ws_dcq, ws_img, ws_done;   /* workspace bytes per frame and the offsets of its parts */
-	size_t lds_bytes;
-} psxhip_mdec_split_geo_t;
+/* one frame across many workgroups (mdec_split.inc; its geometry: mdec_plan.h) */
 typedef struct {
 	const uint8_t *d_frames;
 	uint8_t *d_out;                     /* written by plain stores only: may be page-locked host memory the device can see */
@@ -65,19 +61,13 @@ typedef struct {
 	unsigned long long patience;        /* ticks of the 100 MHz clock a rendezvous waits (0: the default, 0.2 s) */
 	int wh_frame, wh_seg, wh_residue;   /* tests (PSXHIP_MDEC_SPLIT_WITHHOLD): segment wh_seg (0 .. segs - 1; -1: none) of frame wh_frame never arrives */
 } psxhip_mdec_split_t;
-/* 1: the split kernel takes launches of n_frames frames of this geometry (g filled in), 0: it does not */
-int psxhip_mdec_split_geometry(int codec, int width, int height, int max_frame_size, int n_frames, int n_cu, psxhip_mdec_split_geo_t *g);
 hipError_t psxhip_mdec_split_launch(const psxhip_mdec_split_t *a);
 /* psxhip_mdec_encode_batches_device through the frame kernel only (frames the split kernel's watchdog released, encoded again) */
 int psxhip_mdec_encode_batches_frame_kernel(psxhip_mdec_ctx_t *ctx, const psxhip_mdec_batch_t *batches, int n_batches,
                                             size_t frame_stride, int uniform_max_size, size_t out_stride, void *stream);
 
-size_t psxhip_mdec_lds_bytes(int nmb, int out_words, int stg_words, int large);
-int psxhip_mdec_threads_per_group(int large);
 hipError_t psxhip_mdec_upload_tables(void);
 hipError_t psxhip_mdec_set_max_lds(int codec, size_t bytes);
-int psxhip_mdec_pass_order(int width, int height, int large, uint32_t *out, int cap);
-int psxhip_mdec_pass_table(int width, int height, int large, uint32_t *out /* [2 * (n + 1)] */, int cap);
 hipError_t psxhip_mdec_launch(const psxhip_mdec_launch_t *a);
 hipError_t psxhip_mdec_stage_in_launch(const void *src_mapped, void *d_dst, size_t bytes, void *stream);
 hipError_t psxhip_mdec_fdct_launch(const int16_t *d_in, int16_t *d_out, int n_blocks, void *stream);

@@ -853,3 +853,76 @@ def test_host_path_after_fenced_but_still_running_lane_launches(torch_cuda):
                 assert np.array_equal(r[j], want_r) and np.array_equal(o[j], want_o), (rep, k, j)
     assert enc.watchdog() == 0
     enc.close()
+
+
+def _host_call(enc, frames, sizes, out_stride):
+    """psxhip_mdec_encode_frames_host with an out_stride of the caller's choice (the wrapper's is the largest budget): rc, rows, results"""
+    from psxavenc_amd import _lib
+    frames = np.ascontiguousarray(frames, np.uint8)
+    n = frames.shape[0]
+    out, res = np.full((n, out_stride), 0xAA, np.uint8), np.zeros((n, 4), np.int32)
+    if np.isscalar(sizes):
+        sizes_p, uniform = None, int(sizes)
+    else:
+        sizes = np.ascontiguousarray(sizes, np.int32)
+        sizes_p, uniform = sizes.ctypes.data, 0
+    rc = _lib.lib().psxhip_mdec_encode_frames_host(enc._h, frames.ctypes.data, n, sizes_p, uniform, out.ctypes.data, out_stride, res.ctypes.data)
+    return rc, out, res
+
+
+@pytest.mark.parametrize("codec", [0, 1])
+def test_one_context_through_every_host_path_small_larger_small(torch_cuda, codec):
+    """One context through the one-frame call, the chunked call over both staging sets (the first one reused), staging regrown for
+    larger budgets and a wider out_stride, a two-frame call (the split kernel; the staging is kept), the one-frame call again, and
+    device calls either side of split_max: every call's rows and results are those of a fresh context given the same call, the first
+    call's the oracle's too.  48x32 is six macroblocks, fewer than a group has wavefronts: the last round of a pass is partial."""
+    torch = torch_cuda
+    from psxavenc_amd.mdec import query_geometry
+    w, h, ctx_budget = 48, 32, 4096
+    chunk = query_geometry(codec, w, h, ctx_budget).frames_in_flight * 3 // 4
+    assert chunk >= 1
+    n2, n3 = 2 * chunk + 3, chunk + 1
+    fr = O.synth_frames(w, h, n2, seed=61 + codec, amp=3)
+    per_frame = np.array([512, 4096, 1000, 2048] * (n3 // 4 + 1), np.int32)[:n3]
+    host_calls = [(fr[:1], 512, 512), (fr, 512, 512), (fr[:n3], per_frame, 4096 + 64), (fr[5:7], 512, 512), (fr[9:10], 512, 512)]
+    enc = encoder(codec, w, h, ctx_budget)
+    for k, (frames, sizes, stride) in enumerate(host_calls):
+        got = _host_call(enc, frames, sizes, stride)
+        fresh = encoder(codec, w, h, ctx_budget)
+        want = _host_call(fresh, frames, sizes, stride)
+        fresh.close()
+        assert got[0] == want[0] == 0, (k, got[0], want[0])
+        assert_same(got[1], got[2], want[1], want[2], "host call %d" % k)
+        if k == 0:
+            o_out, o_res, orc = O.mdec_encode(codec, w, h, frames, 512)
+            assert orc == 0
+            assert_same(got[1], got[2], o_out, o_res, "host call 0 against the oracle")
+    for n in (12, 13):
+        d = torch.from_numpy(fr[20:20 + n]).to("cuda:0")
+        d_out, d_res = enc.encode_frames_device(d, 512)
+        fresh = encoder(codec, w, h, ctx_budget)
+        w_out, w_res = fresh.encode_frames_device(d, 512)
+        torch.cuda.synchronize()
+        fresh.close()
+        assert_same(d_out.cpu().numpy(), d_res.cpu().numpy(), w_out.cpu().numpy(), w_res.cpu().numpy(), "device call of %d" % n)
+    enc.close()
+
+
+def test_a_failed_creation_leaves_nothing_behind():
+    """a budget 4 bytes past what the LDS takes is refused, twice, and the next context encodes as if nothing had happened"""
+    from psxavenc_amd import _lib
+    from psxavenc_amd.mdec import query_geometry
+    w, h = 48, 32
+    limit = query_geometry(0, w, h, 512).max_frame_size_limit
+    assert limit >= 512
+    for _ in range(2):
+        with pytest.raises(_lib.PsxHipError) as e:
+            encoder(0, w, h, limit + 4)
+        assert e.value.code == _lib.PSXHIP_EINVAL
+    fr = O.synth_frames(w, h, 1, seed=71, amp=3)
+    want, want_res, rc = O.mdec_encode(0, w, h, fr, 512)
+    assert rc == 0
+    enc = encoder(0, w, h, 512)
+    out, res = enc.encode_frames_host(fr, 512)
+    assert_same(out, res, want, want_res, "after two refused creations")
+    enc.close()
