@@ -261,13 +261,16 @@ typedef struct {
 	int32_t unit_stride;     /* record stride, normally 1 (2 for the halves of a stereo pair) */
 } psxhip_adpcm_chain_t;
 
-#define PSXHIP_ADPCM_RECORD_BYTES 32   /* 8-bit codes: byte 0: (shift & 15) | filter << 4; bytes 4..31: the 28 codes.  Also the upper bound of a record's size */
+#define PSXHIP_ADPCM_RECORD_BYTES 32   /* 8-bit codes: byte 0: (shift & 15) | filter << 4; bytes 1..3: zero; bytes 4..31: the 28 codes.  Also the upper bound of a record's size */
 #define PSXHIP_ADPCM_RECORD_BYTES_4BIT 16   /* 4-bit codes (SPU, 4-bit XA): the layout of an SPU block (adpcm.c:367-372): header, 0, 14 bytes of two codes each (even sample low) */
 #define PSXHIP_ADPCM_RECORD_SIZE(bits) ((bits) == 4 ? PSXHIP_ADPCM_RECORD_BYTES_4BIT : PSXHIP_ADPCM_RECORD_BYTES)   /* bytes between the records of consecutive unit indices */
 
 /* Encode n_chains independent chains.  filter_count 5 (SPU) or 4 (XA); bits 4 or 8 (shift range
  * 12 / 8, adpcm.c:29-34).  Output: one record per unit (PSXHIP_ADPCM_RECORD_SIZE(bits) bytes apart, see above) in d_units; d_states[c]
- * is read and updated.  Result per unit == libpsxav/adpcm.c:142-191 encode(). */
+ * is read and updated.  Result per unit == libpsxav/adpcm.c:142-191 encode().  Only the records of the chains' units are written.
+ * d_units is 16-byte aligned when bits == 4 (a 4-bit record is stored, and read by psxhip_spu_pack_device and the sector builders, as
+ * one 16-byte word -- the decoder's entry points ask the same of it) and 4-byte aligned when bits == 8; psxhip_adpcm_session_create
+ * and psxhip_adpcm_encode_chains_chunked likewise.  Anything else is PSXHIP_EINVAL. */
 int psxhip_adpcm_encode_chains_device(int device, const int16_t *d_samples, const psxhip_adpcm_chain_t *d_chains,
                                       const int32_t *d_unit_base, int n_chains, int filter_count, int bits,
                                       psxhip_adpcm_state_t *d_states, uint8_t *d_units, void *stream);
@@ -277,7 +280,8 @@ int psxhip_adpcm_encode_chains_device(int device, const int16_t *d_samples, cons
  * start state (obtained by running `warmup_units` units before the chunk from a zero state), then verify
  * passes re-encode any chunk whose guess differs from its predecessor's actual end state, until a pass changes
  * nothing.  The fixpoint equals the serial encode bit for bit; the guesses only affect speed.  `chains` and
- * `unit_base` are HOST arrays here (the chunk tables are built on the host); the call synchronises.
+ * `unit_base` are HOST arrays here (the chunk tables are built on the host); the call synchronises.  d_states is read and written
+ * in the order of `stream`, like d_samples and d_units: earlier asynchronous work on that stream that updates it is waited for.
  * max_passes <= 0: no limit (the worst case is one chunk per pass).  Returns the number of verify passes
  * (>= 1) or a negative error. */
 int psxhip_adpcm_encode_chains_chunked(int device, const int16_t *d_samples, const psxhip_adpcm_chain_t *chains,
@@ -311,7 +315,7 @@ const char *psxhip_adpcm_kernel_rev(void);
 void psxhip_adpcm_session_reset(psxhip_adpcm_session_t *session);
 void psxhip_adpcm_session_destroy(psxhip_adpcm_session_t *session);
 
-/* Pack n_blocks unit records into 16-byte SPU blocks (adpcm.c:367-372).  d_out 16-byte aligned. */
+/* Pack n_blocks unit records into 16-byte SPU blocks (adpcm.c:367-372).  d_units and d_out 16-byte aligned. */
 int psxhip_spu_pack_device(int device, const uint8_t *d_units, int n_blocks, uint8_t *d_out, void *stream);
 
 /* Assemble XA sectors from unit records in encode order (adpcm.c:193-233,266-332): sector s takes

@@ -11,12 +11,16 @@
 #include "psxhip_internal.h"
 #include "verify_passes.h"
 
+// a 4-bit record is stored and read back as one uint4 (store_spu_block, spu_pack_kernel, the sector kernels): 16 bytes, like the decoder's
+// entry points ask for; an 8-bit record goes out in words
+static bool units_misaligned(const void* d_units, int bits) { return ((uintptr_t)d_units & (bits == 4 ? 15 : 3)) != 0; }
+
 extern "C" int psxhip_adpcm_encode_chains_device(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains,
                                                  const int32_t* d_unit_base, int n_chains, int filter_count, int bits,
                                                  psxhip_adpcm_state_t* d_states, uint8_t* d_units, void* stream) {
     if (!d_samples || !d_chains || !d_unit_base || !d_states || !d_units || n_chains < 0 ||
-        (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || ((uintptr_t)d_units & 3)) {
-        psxhip_set_error("adpcm_encode_chains: bad argument");
+        (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || units_misaligned(d_units, bits)) {
+        psxhip_set_error("adpcm_encode_chains: bad argument (d_units 16-byte aligned for 4-bit records, 4-byte for 8-bit)");
         return PSXHIP_EINVAL;
     }
     int rc = psxhip_ensure_device(device);
@@ -103,8 +107,8 @@ extern "C" int psxhip_adpcm_session_create(psxhip_adpcm_session_t** out, int dev
     if (!out) return PSXHIP_EINVAL;
     *out = nullptr;
     if (!d_samples || !chains || !unit_base || !d_units || n_chains < 0 || (filter_count != 4 && filter_count != 5) ||
-        (bits != 4 && bits != 8) || chunk_units < 1 || warmup_units < 0 || ((uintptr_t)d_units & 3)) {
-        psxhip_set_error("adpcm_session_create: bad argument");
+        (bits != 4 && bits != 8) || chunk_units < 1 || warmup_units < 0 || units_misaligned(d_units, bits)) {
+        psxhip_set_error("adpcm_session_create: bad argument (d_units 16-byte aligned for 4-bit records, 4-byte for 8-bit)");
         return PSXHIP_EINVAL;
     }
     int rc = psxhip_ensure_device(device);
@@ -289,12 +293,20 @@ extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_s
     int rc = psxhip_adpcm_session_create(&s, device, d_samples, chains, unit_base, nullptr, n_chains, filter_count, bits, d_units,
                                          chunk_units, warmup_units, stream);
     if (rc) return rc;
+    // d_states travels on the caller's stream, like everything else here: earlier work on that stream may still be writing it (a serial
+    // psxhip_adpcm_encode_chains_device, say), and a copy on the null stream does not wait for a non-blocking stream
     std::vector<psxhip_adpcm_state_t> st((size_t)n_chains);
-    hipError_t e = hipMemcpy(st.data(), d_states, sizeof(psxhip_adpcm_state_t) * n_chains, hipMemcpyDeviceToHost);
+    const size_t states_bytes = sizeof(psxhip_adpcm_state_t) * (size_t)n_chains;
+    hipStream_t hs = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(st.data(), d_states, states_bytes, hipMemcpyDeviceToHost, hs);
+    if (e == hipSuccess) e = hipStreamSynchronize(hs);
     int passes = PSXHIP_EDEVICE;
     if (e == hipSuccess) {
         passes = psxhip_adpcm_session_run(s, st.data(), nullptr, max_passes, st.data(), nullptr);
-        if (passes >= 0) e = hipMemcpy(d_states, st.data(), sizeof(psxhip_adpcm_state_t) * n_chains, hipMemcpyHostToDevice);
+        if (passes >= 0) {
+            e = hipMemcpyAsync(d_states, st.data(), states_bytes, hipMemcpyHostToDevice, hs);
+            if (e == hipSuccess) e = hipStreamSynchronize(hs);       // the call synchronises (and `st` goes out of scope)
+        }
     }
     psxhip_adpcm_session_destroy(s);
     if (e != hipSuccess) {
@@ -305,8 +317,8 @@ extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_s
 }
 
 extern "C" int psxhip_spu_pack_device(int device, const uint8_t* d_units, int n_blocks, uint8_t* d_out, void* stream) {
-    if (!d_units || !d_out || n_blocks < 0 || ((uintptr_t)d_out & 15) || ((uintptr_t)d_units & 3)) {
-        psxhip_set_error("spu_pack: bad argument (d_out must be 16-byte aligned)");
+    if (!d_units || !d_out || n_blocks < 0 || ((uintptr_t)d_out & 15) || units_misaligned(d_units, 4)) {
+        psxhip_set_error("spu_pack: bad argument (d_units and d_out must be 16-byte aligned)");
         return PSXHIP_EINVAL;
     }
     int rc = psxhip_ensure_device(device);
