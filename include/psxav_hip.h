@@ -708,6 +708,96 @@ int psxhip_str_read_host(psxhip_str_reader_t *reader, const psxhip_str_settings_
 /* revision of the reader's kernels (profiles are keyed by it) */
 const char *psxhip_str_demux_kernel_rev(void);
 
+/* ---------------------------------------------------------------- STRSPU reader -- */
+
+/* The way back for format 8: muxed STRSPU sectors in HBM -> the video rows as above, and the audio chunks de-interleaved into SPU unit
+ * records in the order psxhip_adpcm_decode_chains_* reads.  The rules are "psxhip STRSPU demux v1" (restated in
+ * tests/strspu_demux_ref.py), defined for arbitrary bytes: bad input gives status bits, never a fault.  Symbols are section 15's:
+ * ch = settings->audio_channels (0, 1, 2), B = 126 / ch, L = 16 B, id = strspu_options & 0xFFFF, d = 0 with
+ * PSXHIP_STRSPU_NO_LEADING_DUMMY else 1, loop = the PSXHIP_STRSPU_LOOP bit.
+ *   video   exactly the reader's rules for format 9 (STRV) with settings->str_video_id.
+ *   audio   with ch != 0 a sector is audio iff bytes 0, 1 are 60 01 and le16(2) == id; it is neither video nor other.  ch != 0 with
+ *           str_video_id == -1 or == id, and any undefined strspu_options bit, are PSXHIP_EINVAL.  With ch == 0 no sector is audio.
+ *   number  k = le32(8) - 1 in 64 bits; outside [0, audio_capacity) the sector is dropped: counted in n_dropped_audio, it touches
+ *           nothing.  Of the sectors of one k the one at the lowest stream position is the owner.
+ *   units   by the settings' ch, never the header's: the owner's block b of lane c (16 bytes at 0x20 + c L + 16 b) becomes record
+ *           (k B + b) ch + c of d_units (16-byte records): the lane streams G_c of section 15, one chain per channel with
+ *           unit_stride = ch.  Records of a chunk without an owner are left as they were. */
+enum {
+	PSXHIP_STRSPU_CHUNK_MISSING = 1,     /* no sector carries this number */
+	PSXHIP_STRSPU_CHUNK_DUPLICATE = 2,   /* more than one sector carries this number */
+	PSXHIP_STRSPU_CHUNK_MISMATCH = 4     /* the owner's header is not section 15's for these settings: le16(4) != 0, le16(6) != 1,
+	                                        le32(0xC) != 2016, channels != ch, lane bytes != L, frequency != settings->audio_frequency
+	                                        (when that is non-zero), first sample != (k == 0 ? 0 : 28 (k B - d)), flag bit 1 !=
+	                                        (k == 0 && d), flag bit 2 != loop, or a flag bit above 2 */
+};
+
+typedef struct {
+	int32_t first_sector;        /* the owner's position in the stream, or -1 */
+	int32_t status;              /* PSXHIP_STRSPU_CHUNK_* bits; a chunk without an owner: {-1, MISSING, 0 ...} */
+	int32_t channels;            /* the owner's fields: le16(0x10) */
+	int32_t lane_bytes;          /* le16(0x12) */
+	int32_t frequency;           /* le32(0x14) */
+	int32_t first_sample;        /* le32(0x18) */
+	int32_t flags;               /* le16(0x1C) */
+	int32_t reserved;            /* 0 */
+} psxhip_strspu_chunk_info_t;
+
+typedef struct {
+	int32_t n_chunks;            /* 1 + the highest owned k, or 0 */
+	int32_t n_complete;          /* the k < n_chunks without MISSING */
+	int32_t last_chunk;          /* the lowest owned k whose flag bit 0 (last audio chunk) is set, or -1 */
+	int32_t reserved;
+} psxhip_strspu_audio_summary_t;
+
+/* psxhip_str_demux_device for format 8, on the same handle: the video arguments, their alignment and stride rules are that call's.
+ *   d_units         per stream audio_capacity * 126 records of 16 bytes, 16-byte aligned, streams units_stream_stride bytes (a multiple
+ *                   of 16) apart; may be NULL when audio_capacity is 0.  audio_capacity <= (2^31 - 1) / 126
+ *   d_chunk_info    [n_streams][audio_capacity]; every k in [0, audio_capacity) is written
+ *   d_summary       as psxhip_str_demux_device's: n_audio counts the audio sectors (dropped ones included), n_other does not
+ *   d_audio_summary [n_streams]
+ *   d_sector_table  (optional) audio sectors are {1, -1, k or -1 when dropped, flags & 1}; for a stream this library muxed, read with
+ *                   first_frame 1, the table equals psxhip_str_plan_sectors' and every status is 0
+ * Of the settings str_video_id, audio_channels, audio_frequency (0: not compared), strspu_options, video_width and video_height are
+ * read.  Asynchronous on `stream`; nothing is read back. */
+int psxhip_strspu_demux_device(psxhip_str_reader_t *reader, const psxhip_str_settings_t *settings, int n_streams,
+                               const uint8_t *d_sectors, size_t in_stream_stride, int n_sectors, int64_t first_frame, int max_frames,
+                               uint8_t *d_bs, size_t bs_stride, size_t bs_stream_stride, int32_t *d_bs_sizes,
+                               psxhip_str_frame_info_t *d_frame_info, uint8_t *d_units, int audio_capacity, size_t units_stream_stride,
+                               psxhip_strspu_chunk_info_t *d_chunk_info, psxhip_str_sector_t *d_sector_table,
+                               psxhip_str_summary_t *d_summary, psxhip_strspu_audio_summary_t *d_audio_summary, void *stream);
+
+/* The de-interleave on its own: the inverse of psxhip_strspu_audio_sectors_device, and what an SPUI / VAGI body needs.  Chunk k of
+ * stream i lies at d_in + i * in_stream_stride + (d_src_chunk ? d_src_chunk[k] : k) * chunk_stride; a negative table entry skips the
+ * chunk (its records are left as they were).  Block b of lane c (16 bytes at lane_offset + c * lane_bytes + 16 b of the chunk) becomes
+ * record (k B + b) * channels + c of d_units + i * units_stream_stride, B = lane_bytes / 16.  lane_bytes is a positive multiple of
+ * 16, channels >= 1, lane_offset + channels * lane_bytes <= chunk_stride; d_in, lane_offset and the strides are 4-byte aligned,
+ * d_units and units_stream_stride 16-byte aligned; n_chunks * channels * B fits an int.  An SPUI file from
+ * psxhip_spu_file_encode_host is chunk_stride = align(channels * interleave, alignment), lane_offset = 0, lane_bytes = interleave; a
+ * VAGI file the same with d_in behind its header.  Asynchronous on `stream`. */
+int psxhip_spu_deinterleave_device(int device, const uint8_t *d_in, int n_chunks, size_t chunk_stride, size_t lane_offset,
+                                   size_t lane_bytes, int channels, const int32_t *d_src_chunk, int n_streams, size_t in_stream_stride,
+                                   uint8_t *d_units, size_t units_stream_stride, void *stream);
+
+/* The whole STRSPU reader for one stream in host memory, built like psxhip_str_read_host: H2D, demux, one read-back of the summaries,
+ * the BS decoder over the rows, psxhip_adpcm_decode_chains_chunked over the units (5 filters, 4-bit codes, zero states), D2H.
+ * Channel c is one chain: unit_base = d ch + c, unit_stride = ch, n_units = nK B - d with nK = min(n_chunks, the chunks pcm_capacity
+ * holds, n_sectors), pitch = ch, sample_offset = c.  The units are zeroed first: a missing chunk decodes as silence; the trap block
+ * decodes to 28 zeros, as it lies.
+ *   frames, frame_info, decoded   as psxhip_str_read_host's
+ *   pcm             (optional) room for pcm_capacity int16 (interleaved L,R when stereo): it holds the largest nK with
+ *                   28 (nK B - d) ch <= pcm_capacity; NULL: no audio is taken apart, every audio sector counts as dropped
+ *   chunk_info      (optional) [min(n_sectors, the chunks pcm_capacity holds)]
+ *   audio_summary   (optional)
+ * Returns the samples per channel written to pcm, 28 (nK B - d) or 0, or a value below 0. */
+int psxhip_strspu_read_host(psxhip_str_reader_t *reader, const psxhip_str_settings_t *settings, const uint8_t *sectors, int n_sectors,
+                            int64_t first_frame, int max_frames, uint8_t *frames, psxhip_str_frame_info_t *frame_info,
+                            psxhip_mdec_decoded_t *decoded, int16_t *pcm, int64_t pcm_capacity,
+                            psxhip_strspu_chunk_info_t *chunk_info, psxhip_str_summary_t *summary,
+                            psxhip_strspu_audio_summary_t *audio_summary);
+/* revision of the STRSPU reader's kernels (profiles are keyed by it) */
+const char *psxhip_strspu_demux_kernel_rev(void);
+
 /* ---------------------------------------------------------------- disc finisher -- */
 
 /* The step between "encoded in HBM" and "bytes a drive can read": sectors as the encoders leave them (dummy ECC, file-relative

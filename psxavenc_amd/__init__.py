@@ -13,6 +13,6 @@ from . import adpcm_decode  # noqa: E402,F401  (adpcm_decode.kernel_rev(): the r
 from .adpcm_decode import (adpcm_sse, decode_chains_chunked, decode_chains_device, snr_db, spu_decode_streams,  # noqa: E402,F401
                            xa_decode_streams, xa_disassemble)
 from . import strdemux  # noqa: E402,F401  (strdemux.kernel_rev(): the revision of the STR reader's kernels)
-from .strdemux import StrReader  # noqa: E402,F401
+from .strdemux import StrReader, spu_deinterleave_device  # noqa: E402,F401
 from . import disc  # noqa: E402,F401  (disc.kernel_rev(): the revision of the disc finisher's kernels)
 from .disc import disc_check, disc_finish, disc_plan  # noqa: E402,F401
