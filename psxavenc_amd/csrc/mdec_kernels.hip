@@ -2135,8 +2135,14 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         for (int t0 = 0; t0 < image_words; t0 += job.out_tile) {
             const int t1 = t0 + job.out_tile;
             {
-                // four macroblocks per wavefront, 16 lanes each (a macroblock's stream is typically 6..16 dwords)
-                const int j0 = lane & 15;
+                // v3: four macroblocks per wavefront, 16 lanes each (a macroblock's stream is typically 6..16 dwords).  v2: eight, with
+                // 8 lanes each -- at the headline a stream is 205 bits, seven output dwords, and half of a 16-lane round's slots were
+                // idle.  A stream longer than its lanes takes further turns: a turn moves 64 dwords either way, so longer streams
+                // (16 KiB budgets: fifteen output dwords, two turns of 8 where they took one of 16) pay nothing in turns and half the
+                // rounds' fixed cost.  A constant of the instantiation: as a per-launch choice it needed a scalar register the
+                // 12-wavefront v2 shape does not have (NOTEBOOK, "mdec-k3.10").
+                constexpr int kMbLanes = CODEC == 0 ? 8 : 16, kMbsPerWave = 64 / kMbLanes;
+                const int j0 = lane & (kMbLanes - 1);
                 const int tile = t0 / job.out_tile;
                 int mb_lo = 0, mb_hi = nmb;
                 if (image_words > job.out_tile) {
@@ -2146,8 +2152,8 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     mb_hi = tile + 1 <= kMaxTiles ? L.scalars[S_TILE_FIRST0 + tile + 1] : nmb;
                     for (int u = tile + 2; mb_hi == nmb && u <= kMaxTiles; u++) mb_hi = L.scalars[S_TILE_FIRST0 + u];   // (a tile nobody starts in)
                 }
-                for (int base = mb_lo + wid * 4; base < mb_hi; base += kWavesPerGroup * 4) {
-                    const int mbe = base + (lane >> 4);
+                for (int base = mb_lo + wid * kMbsPerWave; base < mb_hi; base += kWavesPerGroup * kMbsPerWave) {
+                    const int mbe = base + (lane >> (kMbLanes == 16 ? 4 : 3));
                     const bool valid = mbe < mb_hi;
                     const uint32_t r = valid ? L.rec[mbe] : 0u;
                     const int off = (int)(r & 0xFFFFu);
@@ -2156,7 +2162,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     const int g0 = 2 + (int)(D >> 5);             // image dword of this macroblock's first staging dword
                     const uint32_t sh = D & 31u;
                     if (g0 + ndw < t0 || g0 >= t1) ndw = -1;      // nothing of it in this tile
-                    for (int j = j0; wave::ballot(j <= ndw) != 0; j += 16) {
+                    for (int j = j0; wave::ballot(j <= ndw) != 0; j += kMbLanes) {
                         const uint32_t cur = j < ndw ? L.stg[off + j] : 0u;
                         const uint32_t prv = (j >= 1 && j <= ndw) ? L.stg[off + j - 1] : 0u;
                         const uint32_t v = __builtin_amdgcn_alignbit(prv, cur, sh);
