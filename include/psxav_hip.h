@@ -888,6 +888,93 @@ int psxhip_disc_finish_host(int device, const psxhip_disc_layout_t *layout, cons
 /* revision of the finisher's kernels (profiles are keyed by it) */
 const char *psxhip_disc_kernel_rev(void);
 
+/* ---------------------------------------------------------------- disc reader -- */
+
+/* The inverse of the finisher: a raw image of 2352-byte sectors in HBM -> damaged form-1 sectors repaired from their P / Q parity,
+ * every sector routed to a track by file number, channel number and submode, every track's sectors compacted in image order in the
+ * sector size psxhip_str_demux_device (2352 / 2336 / 2048) and psxhip_xa_disassemble_device (2352) read.  The rules are "psxhip disc
+ * read v1" (restated in tests/disc_read_ref.py); they are defined for arbitrary bytes: every index that comes
+ * from the image is bounded before use, bad input gives status bits, never a fault.
+ *
+ * Repair (notation of the finisher's section; S0 = sum c_i, S1 = sum alpha^(n-1-i) c_i over a codeword, parity included; bytes
+ * 0..15 are never altered).  A sector is a form-1 candidate unless bit 0x20 is set in BOTH byte 0x12 and byte 0x16.  On a copy of a
+ * candidate, rounds of a P pass then a Q pass: a codeword with S0 != 0 and S1 != 0 has e = (log S1 - log S0) mod 255; when e < n the
+ * wrong symbol is i = n - 1 - e and, unless it is a header byte, S0 is xored into it (one correction); every other codeword stays.
+ * Rounds repeat until one makes no correction or four have run.  Then the copy is judged as form 1 by check v1: EDC, P and Q all
+ * right -> the sector is form 1 and the copy is its content (repaired when it differs from the input, else clean).  Otherwise the
+ * sector's bytes are the input's, its form is bit 0x20 of byte 0x12, and a form-1 one is unrepairable.  Form 2 sectors are never
+ * altered; their status is PSXHIP_DISC_READ_EDC or _EDC_ABSENT by check v1's rule.
+ *
+ * Routing, on bytes 0x10..0x13 after the repair: (submode & 0x0E) == 0 -> empty, no track.  Else the first track t in list order with
+ * (file_number < 0 || byte 0x10 == file_number) && (channel_number < 0 || (byte 0x11 & 0x1F) == channel_number) &&
+ * (submode & submode_mask) == submode_value; none -> unclaimed.
+ *
+ * Writing: the track's k-th sector in image order goes to sectors + k * stride when k < capacity, else it is dropped and touches
+ * nothing.  sector_size 2352: the whole sector; 2336: bytes 0x10..0x92F; 2048: bytes 0x18..0x817 (a form-2 sector too, which gets
+ * PSXHIP_DISC_READ_FORM).  Bytes between sector_size and stride are never touched. */
+typedef struct {
+	uint8_t *sectors;            /* device memory (psxhip_disc_read_device) or host memory (psxhip_disc_read_host); may be NULL when capacity is 0 */
+	int64_t stride;              /* bytes from one slot to the next: a multiple of 4, >= sector_size */
+	int32_t capacity;            /* slots */
+	int32_t sector_size;         /* 2352, 2336 or 2048 */
+	int32_t file_number;         /* -1: any, else 0 .. 255 */
+	int32_t channel_number;      /* -1: any, else 0 .. 31 */
+	uint8_t submode_mask;
+	uint8_t submode_value;       /* bits outside the mask never match */
+	uint8_t reserved[6];
+} psxhip_disc_track_t;
+
+enum {
+	PSXHIP_DISC_READ_REPAIRED = 1,       /* form 1, made right by `corrections` symbol corrections */
+	PSXHIP_DISC_READ_UNREPAIRABLE = 2,   /* form 1 by byte 0x12 and EDC, P or Q still wrong: the bytes are the input's */
+	PSXHIP_DISC_READ_EDC = 4,            /* form 2: the stored EDC differs from the computed one */
+	PSXHIP_DISC_READ_EDC_ABSENT = 8,     /* form 2: the stored EDC is 0; set instead of PSXHIP_DISC_READ_EDC */
+	PSXHIP_DISC_READ_SYNC = 16,          /* bytes 0..11 are not the sync */
+	PSXHIP_DISC_READ_SUBHEADER = 32,     /* the two subheader copies differ after the repair */
+	PSXHIP_DISC_READ_EMPTY = 64,         /* no video, audio or data bit in the submode: no track */
+	PSXHIP_DISC_READ_UNCLAIMED = 128,    /* no track matches */
+	PSXHIP_DISC_READ_DROPPED = 256,      /* ordinal >= the track's capacity: nothing written */
+	PSXHIP_DISC_READ_FORM = 512          /* a form-2 sector in a 2048-byte track */
+};
+typedef struct {
+	int32_t track;               /* index into the track list, or -1 (empty, unclaimed) */
+	int32_t ordinal;             /* sectors of that track before this one in the image (dropped ones too), or -1 */
+	int32_t status;              /* PSXHIP_DISC_READ_* */
+	int32_t corrections;         /* symbols corrected; 0 unless PSXHIP_DISC_READ_REPAIRED */
+} psxhip_disc_read_sector_t;
+typedef struct {
+	int32_t n_sectors, n_form1, n_form2;
+	int32_t n_clean, n_repaired, n_unrepairable;     /* form 1 = their sum */
+	int32_t n_edc, n_edc_absent;                     /* form 2 */
+	int32_t n_sync, n_subheader, n_empty, n_unclaimed, n_dropped;
+	int32_t reserved;
+	int64_t n_corrections;
+} psxhip_disc_read_summary_t;
+
+typedef struct psxhip_disc_reader psxhip_disc_reader_t;
+/* The handle owns the workspace (16 bytes per sector and 256 per 1024 sectors, grown on demand); calls on one handle are ordered by
+ * the streams they are given: the workspace is reused, so two calls on one handle run on one stream or are ordered by the caller. */
+int psxhip_disc_reader_create(psxhip_disc_reader_t **reader, int device);
+void psxhip_disc_reader_destroy(psxhip_disc_reader_t *reader);
+
+/* d_image: n_sectors x 2352 bytes.  d_sector_table (optional) [n_sectors], d_track_counts [n_tracks] (every track's sectors, dropped
+ * ones included; may be NULL when n_tracks is 0) and *d_summary are overwritten; all device memory.  Refused (PSXHIP_EINVAL, before
+ * any device call): a pointer or stride not 4-byte aligned, stride < sector_size, a sector size other than the three, file or channel
+ * number out of range, capacity < 0, a track with capacity > 0 and no buffer, more than PSXHIP_DISC_MAX_SOURCES tracks, n_sectors < 0
+ * or >= 2^31, a track buffer that overlaps the image or another track's.  Asynchronous on `stream`; nothing is read back;
+ * n_sectors == 0 is fine. */
+int psxhip_disc_read_device(psxhip_disc_reader_t *reader, const uint8_t *d_image, int64_t n_sectors, const psxhip_disc_track_t *tracks,
+                            int n_tracks, psxhip_disc_read_sector_t *d_sector_table, int32_t *d_track_counts,
+                            psxhip_disc_read_summary_t *d_summary, void *stream);
+/* psxhip_disc_read_device for an image, track buffers and results in host memory (no alignment rule for those pointers): H2D of the
+ * image, read, D2H of what was written (slots past a track's count, and bytes between sector_size and stride, stay as they were);
+ * returns when the tracks are written. */
+int psxhip_disc_read_host(psxhip_disc_reader_t *reader, const uint8_t *image, int64_t n_sectors, const psxhip_disc_track_t *tracks,
+                          int n_tracks, psxhip_disc_read_sector_t *sector_table, int32_t *track_counts,
+                          psxhip_disc_read_summary_t *summary);
+/* revision of the reader's kernels (profiles are keyed by it) */
+const char *psxhip_disc_read_kernel_rev(void);
+
 /* ---------------------------------------------------------------- SPU / VAG / SPUI / VAGI files ---- */
 
 /* The reference's encode_file_spu / encode_file_spui (psxavenc/filefmt.c:212-389, .vag header :95-162) for PCM that is

@@ -16,3 +16,5 @@ from . import strdemux  # noqa: E402,F401  (strdemux.kernel_rev(): the revision 
 from .strdemux import StrReader, spu_deinterleave_device  # noqa: E402,F401
 from . import disc  # noqa: E402,F401  (disc.kernel_rev(): the revision of the disc finisher's kernels)
 from .disc import disc_check, disc_finish, disc_plan  # noqa: E402,F401
+from . import discread  # noqa: E402,F401  (discread.kernel_rev(): the revision of the disc reader's kernels)
+from .discread import DiscReader, disc_read, disc_read_host  # noqa: E402,F401
