@@ -68,6 +68,30 @@ def lib():
     return L
 
 
+def launch_stream(stream, device):
+    """The stream a wrapper launches on: the caller's `stream`, else the current stream of `device`."""
+    import torch
+    return stream if stream is not None else torch.cuda.current_stream(device)
+
+
+def new_tensor(stream, device, shape, dtype, fill=None):
+    """The one way a wrapper creates a device tensor: allocated, and filled with `fill` (None: left as it is), with the launch
+    stream current.  The fill is then ordered before the library's kernels on that stream, whatever the caller's current stream is
+    doing, and the caching allocator knows the block as that stream's: it is not handed out again under a running launch."""
+    import torch
+    with torch.cuda.stream(launch_stream(stream, device)):
+        if fill is None:
+            return torch.empty(shape, dtype=dtype, device=device)
+        return torch.zeros(shape, dtype=dtype, device=device) if fill == 0 else torch.full(shape, fill, dtype=dtype, device=device)
+
+
+def to_device(stream, device, array):
+    """A host numpy array as a device tensor of the launch stream (the same rule as new_tensor, for the tables a wrapper uploads)."""
+    import torch
+    with torch.cuda.stream(launch_stream(stream, device)):
+        return torch.from_numpy(array).to(device)
+
+
 def check(rc):
     if rc != 0:
         raise PsxHipError(rc, lib().psxhip_last_error().decode("utf-8", "replace"))

@@ -196,12 +196,13 @@ def make_chains(offsets, pitch, limits, n_units, unit_stride=1):
 
 
 def encode_chains_device(d_samples, chains, unit_base, filter_count, bits, d_states=None, d_units=None, chunk_units=0,
-                         warmup_units=16, max_passes=0):
+                         warmup_units=16, max_passes=0, stream=None):
     """Run the ADPCM search for `chains` (host CHAIN_DTYPE array) over int16 CUDA tensor `d_samples`.
 
     chunk_units == 0: one serial pass per chain (psxhip_adpcm_encode_chains_device, asynchronous).
     chunk_units  > 0: speculate-and-verify along time (psxhip_adpcm_encode_chains_chunked, synchronous).
-    Returns (d_units (total_units, record_bytes(bits)) uint8, d_states (n_chains, 2) int32, verify_passes)."""
+    Returns (d_units (total_units, record_bytes(bits)) uint8, d_states (n_chains, 2) int32, verify_passes).
+    stream: the stream of the launches (None: the current one); the Python call waits for it either way."""
     import torch
     L = _bind()
     L.psxhip_adpcm_encode_chains_chunked.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -212,10 +213,10 @@ def encode_chains_device(d_samples, chains, unit_base, filter_count, bits, d_sta
     n = chains.size
     total = int((unit_base + (chains["n_units"] - 1) * chains["unit_stride"]).max()) + 1 if n else 0
     if d_states is None:
-        d_states = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        d_states = _lib.new_tensor(stream, dev, (n, 2), torch.int32, 0)
     if d_units is None:
-        d_units = torch.zeros((max(total, 1), record_bytes(bits)), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
+        d_units = _lib.new_tensor(stream, dev, (max(total, 1), record_bytes(bits)), torch.uint8, 0)
+    st = _lib.launch_stream(stream, dev).cuda_stream
     if chunk_units > 0:
         rc = L.psxhip_adpcm_encode_chains_chunked(dev.index or 0, d_samples.data_ptr(), chains.ctypes.data, unit_base.ctypes.data,
                                                   n, filter_count, bits, d_states.data_ptr(), d_units.data_ptr(), chunk_units,
@@ -223,29 +224,29 @@ def encode_chains_device(d_samples, chains, unit_base, filter_count, bits, d_sta
         if rc < 0:
             _lib.check(rc)
         return d_units, d_states, rc
-    d_chains = torch.from_numpy(chains.view(np.uint8).reshape(n, CHAIN_DTYPE.itemsize).copy()).to(dev)
-    d_base = torch.from_numpy(unit_base).to(dev)
+    d_chains = _lib.to_device(stream, dev, chains.view(np.uint8).reshape(n, CHAIN_DTYPE.itemsize).copy())
+    d_base = _lib.to_device(stream, dev, unit_base)
     _lib.check(L.psxhip_adpcm_encode_chains_device(dev.index or 0, d_samples.data_ptr(), d_chains.data_ptr(), d_base.data_ptr(), n,
                                                    filter_count, bits, d_states.data_ptr(), d_units.data_ptr(), st))
-    torch.cuda.current_stream(dev).synchronize()    # d_chains / d_base are temporaries
+    _lib.launch_stream(stream, dev).synchronize()    # d_chains / d_base are temporaries
     return d_units, d_states, 0
 
 
-def spu_pack_device(d_units, n_blocks):
+def spu_pack_device(d_units, n_blocks, stream=None):
     import torch
     L = _bind()
-    out = torch.empty((n_blocks, 16), dtype=torch.uint8, device=d_units.device)
-    st = torch.cuda.current_stream(d_units.device).cuda_stream
+    out = _lib.new_tensor(stream, d_units.device, (n_blocks, 16), torch.uint8)
+    st = _lib.launch_stream(stream, d_units.device).cuda_stream
     _lib.check(L.psxhip_spu_pack_device(d_units.device.index or 0, d_units.data_ptr(), n_blocks, out.data_ptr(), st))
     return out
 
 
-def xa_assemble_device(d_units, n_sectors, settings, first_lba=0, d_eof=None):
+def xa_assemble_device(d_units, n_sectors, settings, first_lba=0, d_eof=None, stream=None):
     import torch
     L = _bind()
     ssz = xa_get_buffer_size_per_sector(settings)
-    out = torch.empty((n_sectors, ssz), dtype=torch.uint8, device=d_units.device)
-    st = torch.cuda.current_stream(d_units.device).cuda_stream
+    out = _lib.new_tensor(stream, d_units.device, (n_sectors, ssz), torch.uint8)
+    st = _lib.launch_stream(stream, d_units.device).cuda_stream
     _lib.check(L.psxhip_xa_assemble_device(d_units.device.index or 0, d_units.data_ptr(), n_sectors, settings.format,
                                            int(settings.stereo), settings.frequency, settings.bits_per_sample,
                                            settings.file_number, settings.channel_number, first_lba,
@@ -297,7 +298,7 @@ class AdpcmSession:
         self.n_chains = self.chains.size
         dev = d_samples.device
         total = int((self.unit_base + (self.chains["n_units"] - 1) * self.chains["unit_stride"]).max()) + 1 if self.n_chains else 0
-        self.d_units = d_units if d_units is not None else torch.zeros((max(total, 1), record_bytes(bits)), dtype=torch.uint8, device=dev)
+        self.d_units = d_units if d_units is not None else _lib.new_tensor(None, dev, (max(total, 1), record_bytes(bits)), torch.uint8, 0)
         self.d_samples = d_samples          # keep alive
         lead = None if lead_units is None else np.ascontiguousarray(lead_units, dtype=np.int32)
         self._h = C.c_void_p()

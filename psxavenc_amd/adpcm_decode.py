@@ -60,15 +60,15 @@ def _ptr(t):
 
 
 def _stream(dev, stream):
-    return (stream if stream is not None else torch.cuda.current_stream(dev)).cuda_stream
+    return _lib.launch_stream(stream, dev).cuda_stream
 
 
-def _chain_tensors(chains, unit_base, dev):
+def _chain_tensors(chains, unit_base, dev, stream):
     chains = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
     unit_base = np.ascontiguousarray(unit_base, dtype=np.int32)
     assert chains.size == unit_base.size
-    d_chains = torch.from_numpy(chains.view(np.uint8).reshape(chains.size, CHAIN_DTYPE.itemsize).copy()).to(dev)
-    return chains, unit_base, d_chains, torch.from_numpy(unit_base.copy()).to(dev)
+    d_chains = _lib.to_device(stream, dev, chains.view(np.uint8).reshape(chains.size, CHAIN_DTYPE.itemsize).copy())
+    return chains, unit_base, d_chains, _lib.to_device(stream, dev, unit_base.copy())
 
 
 def decode_chains_device(d_units, chains, unit_base, filter_count, bits, d_samples, d_states=None, d_unit_flags=None, d_tail=None,
@@ -79,13 +79,13 @@ def decode_chains_device(d_units, chains, unit_base, filter_count, bits, d_sampl
     d_tail: (n_chains, 28) int16, the unit sample_limit cuts.  Returns d_states; the call waits for the stream (the chain tables it
     uploaded are temporaries)."""
     dev = d_units.device
-    chains, unit_base, d_chains, d_base = _chain_tensors(chains, unit_base, dev)
+    chains, unit_base, d_chains, d_base = _chain_tensors(chains, unit_base, dev, stream)
     if d_states is None:
-        d_states = torch.zeros((chains.size, 2), dtype=torch.int32, device=dev)
+        d_states = _lib.new_tensor(stream, dev, (chains.size, 2), torch.int32, 0)
     _lib.check(_bind().psxhip_adpcm_decode_chains_device(dev.index or 0, d_units.data_ptr(), d_chains.data_ptr(), d_base.data_ptr(),
                                                          chains.size, filter_count, bits, d_states.data_ptr(), d_samples.data_ptr(),
                                                          _ptr(d_unit_flags), _ptr(d_tail), _stream(dev, stream)))
-    (stream if stream is not None else torch.cuda.current_stream(dev)).synchronize()
+    _lib.launch_stream(stream, dev).synchronize()
     return d_states
 
 
@@ -98,7 +98,7 @@ def decode_chains_chunked(d_units, chains, unit_base, filter_count, bits, d_samp
     chains = np.ascontiguousarray(chains, dtype=CHAIN_DTYPE)
     unit_base = np.ascontiguousarray(unit_base, dtype=np.int32)
     if d_states is None:
-        d_states = torch.zeros((chains.size, 2), dtype=torch.int32, device=dev)
+        d_states = _lib.new_tensor(stream, dev, (chains.size, 2), torch.int32, 0)
     rc = _bind().psxhip_adpcm_decode_chains_chunked(dev.index or 0, d_units.data_ptr(), chains.ctypes.data, unit_base.ctypes.data,
                                                     chains.size, filter_count, bits, d_states.data_ptr(), d_samples.data_ptr(),
                                                     _ptr(d_unit_flags), _ptr(d_tail), chunk_units, warmup_units, max_passes,
@@ -114,17 +114,17 @@ def adpcm_sse(d_a, d_b, chains, unit_base=None, d_a_tail=None, n_records=None, c
     [sum (a - b)^2, sum b^2] -- int64 tensors holding the library's uint64.  d_a_tail: the decode call's d_tail."""
     dev = d_a.device
     base = np.zeros(len(chains), np.int32) if unit_base is None else unit_base
-    chains, base, d_chains, d_base = _chain_tensors(chains, base, dev)
+    chains, base, d_chains, d_base = _chain_tensors(chains, base, dev, stream)
     d_unit = None
     if unit_base is not None:
         if n_records is None:
             n_records = int((base + (chains["n_units"] - 1) * chains["unit_stride"]).max()) + 1 if chains.size else 0
-        d_unit = torch.zeros(max(n_records, 1), dtype=torch.int64, device=dev)
-    d_sums = torch.zeros((chains.size, 2), dtype=torch.int64, device=dev) if chain_sums else None
+        d_unit = _lib.new_tensor(stream, dev, (max(n_records, 1),), torch.int64, 0)
+    d_sums = _lib.new_tensor(stream, dev, (chains.size, 2), torch.int64, 0) if chain_sums else None
     _lib.check(_bind().psxhip_adpcm_sse_device(dev.index or 0, d_a.data_ptr(), _ptr(d_a_tail), d_b.data_ptr(), d_chains.data_ptr(),
                                                chains.size, _ptr(d_unit), d_base.data_ptr() if d_unit is not None else None,
                                                _ptr(d_sums), _stream(dev, stream)))
-    (stream if stream is not None else torch.cuda.current_stream(dev)).synchronize()
+    _lib.launch_stream(stream, dev).synchronize()
     return d_unit, d_sums
 
 
@@ -136,8 +136,8 @@ def xa_disassemble(d_sectors, settings, d_units=None, stream=None):
     bits = settings.bits_per_sample
     assert d_sectors.dtype == torch.uint8 and d_sectors.is_contiguous() and d_sectors.shape[1] == (2336 if settings.format == 0 else 2352)
     if d_units is None:
-        d_units = torch.zeros((max(n, 1) * 18 * (8 if bits == 4 else 4), record_bytes(bits)), dtype=torch.uint8, device=dev)
-    d_status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        d_units = _lib.new_tensor(stream, dev, (max(n, 1) * 18 * (8 if bits == 4 else 4), record_bytes(bits)), torch.uint8, 0)
+    d_status = _lib.new_tensor(stream, dev, (max(n, 1),), torch.int32, 0)
     _lib.check(_bind().psxhip_xa_disassemble_device(dev.index or 0, d_sectors.data_ptr(), n, settings.format, int(settings.stereo),
                                                     settings.frequency, bits, d_units.data_ptr(), d_status.data_ptr(),
                                                     _stream(dev, stream)))

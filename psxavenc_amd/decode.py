@@ -82,15 +82,15 @@ class MdecDecoder:
             assert sizes.is_cuda and sizes.dtype == torch.int32 and sizes.numel() == n and sizes.is_contiguous()
             sizes_p, uniform = sizes.data_ptr(), 0
         if d_levels is None and levels:
-            d_levels = torch.empty((n, self.blocks, 64), dtype=torch.int16, device=d_bs.device)
+            d_levels = _lib.new_tensor(stream, d_bs.device, (n, self.blocks, 64), torch.int16)
         if d_frames is None and frames:
-            d_frames = torch.zeros((n, self.frame_bytes), dtype=torch.uint8, device=d_bs.device)
+            d_frames = _lib.new_tensor(stream, d_bs.device, (n, self.frame_bytes), torch.uint8, 0)
         if d_decoded is None:
-            d_decoded = torch.zeros((n, 4), dtype=torch.int32, device=d_bs.device)
+            d_decoded = _lib.new_tensor(stream, d_bs.device, (n, 4), torch.int32, 0)
         assert d_levels is None or (d_levels.dtype == torch.int16 and d_levels.is_contiguous() and d_levels.numel() == n * self.blocks * 64)
         assert d_frames is None or (d_frames.dtype == torch.uint8 and d_frames.dim() == 2 and d_frames.shape[0] == n)
         assert d_decoded.dtype == torch.int32 and d_decoded.is_contiguous() and d_decoded.numel() == n * 4
-        st = stream if stream is not None else torch.cuda.current_stream(d_bs.device)
+        st = _lib.launch_stream(stream, d_bs.device)
         _lib.check(_bind().psxhip_mdec_decode_frames_device(
             self._h, d_bs.data_ptr(), d_bs.stride(0), sizes_p, uniform, n, d_levels.data_ptr() if d_levels is not None else None,
             d_frames.data_ptr() if d_frames is not None else None, d_frames.stride(0) if d_frames is not None else 0,
@@ -123,9 +123,9 @@ def sse_device(d_a, d_b, width, height, d_sse=None, stream=None):
     assert d_a.dim() == 2 and d_a.shape[0] == d_b.shape[0] and d_a.stride(0) == d_b.stride(0)
     n = d_a.shape[0]
     if d_sse is None:
-        d_sse = torch.zeros((n, 3), dtype=torch.int64, device=d_a.device)
+        d_sse = _lib.new_tensor(stream, d_a.device, (n, 3), torch.int64, 0)
     assert d_sse.dtype == torch.int64 and d_sse.is_contiguous() and d_sse.numel() == n * 3
-    st = stream if stream is not None else torch.cuda.current_stream(d_a.device)
+    st = _lib.launch_stream(stream, d_a.device)
     _lib.check(_bind().psxhip_mdec_sse_device(d_a.device.index or 0, d_a.data_ptr(), d_b.data_ptr(), d_a.stride(0), width, height, n,
                                               d_sse.data_ptr(), st.cuda_stream))
     return d_sse

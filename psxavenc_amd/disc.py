@@ -111,9 +111,9 @@ def disc_finish(lay, sources, first_out=0, n_out=None, d_out=None, device=0, str
         n_out = disc_plan(lay, sources) - first_out
     dev = torch.device("cuda", device)
     if d_out is None:
-        d_out = torch.empty((max(n_out, 0), 2352), dtype=torch.uint8, device=dev)
+        d_out = _lib.new_tensor(stream, dev, (max(n_out, 0), 2352), torch.uint8)
     assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.numel() >= n_out * 2352
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    st = _lib.launch_stream(stream, dev)
     _lib.check(_bind().psxhip_disc_finish_device(device, C.byref(lay), _table(sources), len(sources), d_out.data_ptr(), first_out, n_out,
                                                  st.cuda_stream))
     return d_out
@@ -125,9 +125,9 @@ def disc_check(d_image, start_lba=-1, status=True, stream=None):
     assert torch is not None and d_image.is_cuda and d_image.dtype == torch.uint8 and d_image.is_contiguous()
     n = d_image.numel() // 2352
     dev = d_image.device
-    d_status = torch.zeros((n,), dtype=torch.int32, device=dev) if status else None
-    d_summary = torch.zeros((12,), dtype=torch.int32, device=dev)
-    st = stream if stream is not None else torch.cuda.current_stream(dev)
+    d_status = _lib.new_tensor(stream, dev, (n,), torch.int32, 0) if status else None
+    d_summary = _lib.new_tensor(stream, dev, (12,), torch.int32, 0)
+    st = _lib.launch_stream(stream, dev)
     _lib.check(_bind().psxhip_disc_check_device(dev.index or 0, d_image.data_ptr() if n else None, n, int(start_lba),
                                                 d_status.data_ptr() if status else None, d_summary.data_ptr(), st.cuda_stream))
     return d_status, d_summary

@@ -124,10 +124,10 @@ class DiscReader:
         assert torch is not None and d_image.is_cuda and d_image.dtype == torch.uint8 and d_image.is_contiguous()
         n = d_image.numel() // 2352
         dev = d_image.device
-        d_table = torch.zeros((n, 4), dtype=torch.int32, device=dev) if table else None
-        d_counts = torch.zeros((max(1, len(tracks)),), dtype=torch.int32, device=dev)
-        d_summary = torch.zeros((16,), dtype=torch.int32, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        d_table = _lib.new_tensor(stream, dev, (n, 4), torch.int32, 0) if table else None
+        d_counts = _lib.new_tensor(stream, dev, (max(1, len(tracks)),), torch.int32, 0)
+        d_summary = _lib.new_tensor(stream, dev, (16,), torch.int32, 0)
+        st = _lib.launch_stream(stream, dev)
         _lib.check(_bind().psxhip_disc_read_device(self._h, d_image.data_ptr() if n else None, n, _table(tracks), len(tracks),
                                                    d_table.data_ptr() if table and n else None, d_counts.data_ptr(), d_summary.data_ptr(),
                                                    st.cuda_stream))
@@ -154,7 +154,7 @@ def disc_read(d_image, tracks, reader=None, table=True, stream=None):
     r = DiscReader(d_image.device.index or 0)
     try:
         out = r.read_device(d_image, tracks, table, stream)
-        (stream if stream is not None else torch.cuda.current_stream(d_image.device)).synchronize()
+        _lib.launch_stream(stream, d_image.device).synchronize()
         return out
     finally:
         r.close()

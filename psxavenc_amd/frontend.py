@@ -71,8 +71,8 @@ class Scaler:
         assert d_pictures.is_cuda and d_pictures.dtype == torch.uint8 and d_pictures.dim() == 2
         n = d_pictures.shape[0]
         if d_frames is None:
-            d_frames = torch.empty((n, self.frame_bytes), dtype=torch.uint8, device=d_pictures.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_pictures.device)
+            d_frames = _lib.new_tensor(stream, d_pictures.device, (n, self.frame_bytes), torch.uint8)
+        st = _lib.launch_stream(stream, d_pictures.device)
         _lib.check(_bind().psxhip_scaler_convert_device(self._h, d_pictures.data_ptr(), d_pictures.stride(0), n, d_frames.data_ptr(),
                                                         d_frames.stride(0), st.cuda_stream))
         return d_frames

@@ -102,10 +102,10 @@ class MdecEncoder:
             sizes_p, uniform, mx = frame_max_sizes.data_ptr(), 0, self.max_frame_size
         ostride = (mx + 3) & ~3
         if d_out is None:
-            d_out = torch.zeros((n, ostride), dtype=torch.uint8, device=d_frames.device)
+            d_out = _lib.new_tensor(stream, d_frames.device, (n, ostride), torch.uint8, 0)
         if d_results is None:
-            d_results = torch.zeros((n, 4), dtype=torch.int32, device=d_frames.device)
-        st = stream if stream is not None else torch.cuda.current_stream(d_frames.device)
+            d_results = _lib.new_tensor(stream, d_frames.device, (n, 4), torch.int32, 0)
+        st = _lib.launch_stream(stream, d_frames.device)
         rc = _lib.lib().psxhip_mdec_encode_frames_device(self._h, d_frames.data_ptr(), d_frames.stride(0), n, sizes_p,
                                                          uniform, d_out.data_ptr(), d_out.stride(0),
                                                          d_results.data_ptr(), st.cuda_stream)
@@ -130,7 +130,7 @@ class MdecEncoder:
                 ostride = d_out.stride(0) if ostride is None else ostride
                 assert d_frames.stride(0) == fstride and d_out.stride(0) == ostride, "batches share their row strides"
             arr[i] = MdecBatch(d_frames.data_ptr(), n, 0, d_sizes.data_ptr() if d_sizes is not None else None, d_out.data_ptr(), d_res.data_ptr())
-        st = stream if stream is not None else torch.cuda.current_stream(batches[0][0].device)
+        st = _lib.launch_stream(stream, batches[0][0].device)
         L = _lib.lib()
         L.psxhip_mdec_encode_batches_device.argtypes = [C.c_void_p, C.POINTER(MdecBatch), C.c_int, C.c_size_t, C.c_int, C.c_size_t, C.c_void_p]
         _lib.check(L.psxhip_mdec_encode_batches_device(self._h, arr, len(batches), fstride or self.frame_bytes, int(frame_max_size),
@@ -147,7 +147,7 @@ class MdecEncoder:
         """psxhip_mdec_fence: order `stream` behind every launch of this context issued so far"""
         L = _lib.lib()
         L.psxhip_mdec_fence.argtypes = [C.c_void_p, C.c_void_p]
-        st = stream if stream is not None else torch.cuda.current_stream(torch.device("cuda", self.device))
+        st = _lib.launch_stream(stream, torch.device("cuda", self.device))
         _lib.check(L.psxhip_mdec_fence(self._h, st.cuda_stream))
 
     def watchdog(self):

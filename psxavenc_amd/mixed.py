@@ -80,10 +80,10 @@ def frames_host(oracle_lib, w, h, seed, first, n):
 def frames_device(w, h, seed, first, n, device=0):
     """the same frames in HBM: (n, w*h*3/2) uint8 CUDA tensor"""
     import torch
-    from . import synth
+    from . import _lib, synth
     fr, runs = plan(seed, first + n)
     dev = torch.device("cuda", device)
-    out = torch.empty((n, w * h * 3 // 2), dtype=torch.uint8, device=dev)
+    out = _lib.new_tensor(None, dev, (n, w * h * 3 // 2), torch.uint8)
     for (r0, cnt, amp, rseed) in runs:
         a, b = max(r0, first), min(r0 + cnt, first + n)
         if a < b:
@@ -93,6 +93,6 @@ def frames_device(w, h, seed, first, n, device=0):
         kind, k, _ = fr[first + i]
         if kind == "special":
             if k not in cache:
-                cache[k] = torch.from_numpy(special_frame(k, w, h)).to(dev)
+                cache[k] = _lib.to_device(None, dev, special_frame(k, w, h))
             out[i].copy_(cache[k])
     return out

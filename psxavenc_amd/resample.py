@@ -145,9 +145,9 @@ class Resampler:
             ptrs = self._pointers([d_pcm.data_ptr()])
         want = self.output_count(n, flush)
         if d_out is None:
-            d_out = torch.empty((want, self.dst_channels), dtype=torch.int16, device=d_pcm.device)
+            d_out = _lib.new_tensor(stream, d_pcm.device, (want, self.dst_channels), torch.int16)
         assert d_out.is_contiguous() and d_out.numel() >= want * self.dst_channels
-        st = stream if stream is not None else torch.cuda.current_stream(d_pcm.device)
+        st = _lib.launch_stream(stream, d_pcm.device)
         got = C.c_int64()
         _lib.check(_bind().psxhip_resampler_convert_device(self._h, ptrs, n, d_out.data_ptr() if want else None, C.byref(got),
                                                            int(bool(flush)), st.cuda_stream))

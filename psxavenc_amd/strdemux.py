@@ -84,10 +84,10 @@ def spu_deinterleave_device(d_in, lane_bytes, channels, lane_offset=0, d_src_chu
         assert d_src_chunk.dtype == torch.int32 and d_src_chunk.is_contiguous() and d_src_chunk.shape[0] >= n_chunks
     records = n_chunks * channels * (lane_bytes // 16)
     if d_units is None:
-        d_units = torch.zeros((S, records, 16), dtype=torch.uint8, device=d_in.device)
+        d_units = _lib.new_tensor(stream, d_in.device, (S, records, 16), torch.uint8, 0)
     assert d_units.dtype == torch.uint8 and tuple(d_units.shape) == (S, records, 16) and d_units.stride(2) == 1
     assert records == 0 or d_units.stride(1) == 16
-    st = stream if stream is not None else torch.cuda.current_stream(d_in.device)
+    st = _lib.launch_stream(stream, d_in.device)
     _lib.check(_bind().psxhip_spu_deinterleave_device(
         d_in.device.index or 0, d_in.data_ptr(), n_chunks, d_in.stride(1), lane_offset, lane_bytes, channels, _ptr(d_src_chunk), S,
         d_in.stride(0) if S > 1 else 0, d_units.data_ptr(), d_units.stride(0) if S > 1 else 0, st.cuda_stream))
@@ -131,22 +131,22 @@ class StrReader:
         if xa_capacity is None:
             xa_capacity = n
         if d_bs is None:
-            d_bs = torch.zeros((S, max_frames, bs_stride), dtype=torch.uint8, device=dev)
+            d_bs = _lib.new_tensor(stream, dev, (S, max_frames, bs_stride), torch.uint8, 0)
         if d_sizes is None:
-            d_sizes = torch.zeros((S, max_frames), dtype=torch.int32, device=dev)
+            d_sizes = _lib.new_tensor(stream, dev, (S, max_frames), torch.int32, 0)
         if d_info is None:
-            d_info = torch.zeros((S, max_frames, 8), dtype=torch.int32, device=dev)
+            d_info = _lib.new_tensor(stream, dev, (S, max_frames, 8), torch.int32, 0)
         if d_xa is None:
-            d_xa = torch.zeros((S, xa_capacity, ssz), dtype=torch.uint8, device=dev)
+            d_xa = _lib.new_tensor(stream, dev, (S, xa_capacity, ssz), torch.uint8, 0)
         if d_table is None and table:
-            d_table = torch.zeros((S, n, 4), dtype=torch.int32, device=dev)
+            d_table = _lib.new_tensor(stream, dev, (S, n, 4), torch.int32, 0)
         if d_summary is None:
-            d_summary = torch.zeros((S, 8), dtype=torch.int32, device=dev)
+            d_summary = _lib.new_tensor(stream, dev, (S, 8), torch.int32, 0)
         assert d_bs.dtype == torch.uint8 and tuple(d_bs.shape) == (S, max_frames, bs_stride) and d_bs.stride(2) == 1
         assert d_xa.dtype == torch.uint8 and tuple(d_xa.shape) == (S, xa_capacity, ssz) and (xa_capacity == 0 or d_xa.stride(1) == ssz)
         for t, shape in ((d_sizes, (S, max_frames)), (d_info, (S, max_frames, 8)), (d_summary, (S, 8))) + (((d_table, (S, n, 4)),) if d_table is not None else ()):
             assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        st = _lib.launch_stream(stream, dev)
         assert max_frames == 0 or d_bs.stride(1) == bs_stride, "a row's pitch is bs_stride: room behind the last whole chunk is the row's margin"
         _lib.check(_bind().psxhip_str_demux_device(
             self._h, C.byref(s), S, d_sectors.data_ptr(), d_sectors.stride(0) if S > 1 else 0, n, int(first_frame), max_frames,
@@ -202,28 +202,28 @@ class StrReader:
         if audio_capacity is None:
             audio_capacity = n
         if d_bs is None:
-            d_bs = torch.zeros((S, max_frames, bs_stride), dtype=torch.uint8, device=dev)
+            d_bs = _lib.new_tensor(stream, dev, (S, max_frames, bs_stride), torch.uint8, 0)
         if d_sizes is None:
-            d_sizes = torch.zeros((S, max_frames), dtype=torch.int32, device=dev)
+            d_sizes = _lib.new_tensor(stream, dev, (S, max_frames), torch.int32, 0)
         if d_info is None:
-            d_info = torch.zeros((S, max_frames, 8), dtype=torch.int32, device=dev)
+            d_info = _lib.new_tensor(stream, dev, (S, max_frames, 8), torch.int32, 0)
         if d_units is None:
-            d_units = torch.zeros((S, audio_capacity * 126, 16), dtype=torch.uint8, device=dev)
+            d_units = _lib.new_tensor(stream, dev, (S, audio_capacity * 126, 16), torch.uint8, 0)
         if d_chunk_info is None:
-            d_chunk_info = torch.zeros((S, audio_capacity, 8), dtype=torch.int32, device=dev)
+            d_chunk_info = _lib.new_tensor(stream, dev, (S, audio_capacity, 8), torch.int32, 0)
         if d_table is None and table:
-            d_table = torch.zeros((S, n, 4), dtype=torch.int32, device=dev)
+            d_table = _lib.new_tensor(stream, dev, (S, n, 4), torch.int32, 0)
         if d_summary is None:
-            d_summary = torch.zeros((S, 8), dtype=torch.int32, device=dev)
+            d_summary = _lib.new_tensor(stream, dev, (S, 8), torch.int32, 0)
         if d_audio_summary is None:
-            d_audio_summary = torch.zeros((S, 4), dtype=torch.int32, device=dev)
+            d_audio_summary = _lib.new_tensor(stream, dev, (S, 4), torch.int32, 0)
         assert d_bs.dtype == torch.uint8 and tuple(d_bs.shape) == (S, max_frames, bs_stride) and d_bs.stride(2) == 1
         assert d_units.dtype == torch.uint8 and tuple(d_units.shape) == (S, audio_capacity * 126, 16) and d_units.stride(2) == 1
         assert audio_capacity == 0 or d_units.stride(1) == 16
         for t, shape in ((d_sizes, (S, max_frames)), (d_info, (S, max_frames, 8)), (d_summary, (S, 8)), (d_audio_summary, (S, 4)),
                          (d_chunk_info, (S, audio_capacity, 8))) + (((d_table, (S, n, 4)),) if d_table is not None else ()):
             assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        st = _lib.launch_stream(stream, dev)
         assert max_frames == 0 or d_bs.stride(1) == bs_stride, "a row's pitch is bs_stride: room behind the last whole chunk is the row's margin"
         _lib.check(_bind().psxhip_strspu_demux_device(
             self._h, C.byref(s), S, d_sectors.data_ptr(), d_sectors.stride(0) if S > 1 else 0, n, int(first_frame), max_frames,

@@ -73,13 +73,13 @@ def strspu_audio_sectors_device(d_units, n_sectors, channels, frequency, options
     n_streams = d_units.shape[0]
     if d_out is None:
         assert d_dst_sector is None
-        d_out = torch.zeros((n_streams, n_sectors, 2048), dtype=torch.uint8, device=d_units.device)
+        d_out = _lib.new_tensor(stream, d_units.device, (n_streams, n_sectors, 2048), torch.uint8, 0)
     assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and d_out.dim() == 3 and d_out.shape[0] == n_streams and d_out.shape[2] == 2048
     if d_dst_sector is not None:
         assert d_dst_sector.is_cuda and d_dst_sector.dtype == torch.int32 and d_dst_sector.is_contiguous() and d_dst_sector.numel() == n_sectors
     else:
         assert d_out.shape[1] >= n_sectors
-    st = stream if stream is not None else torch.cuda.current_stream(d_units.device)
+    st = _lib.launch_stream(stream, d_units.device)
     _lib.check(_bind().psxhip_strspu_audio_sectors_device(
         d_units.device.index or 0, d_units.data_ptr(), n_sectors, channels, frequency, options, n_streams, d_units.stride(0), d_out.data_ptr(),
         d_dst_sector.data_ptr() if d_dst_sector is not None else None, d_out.stride(0), st.cuda_stream))
@@ -178,9 +178,9 @@ class StrMuxer:
             per_ch = d_pcm.shape[1] // ch if s.audio_channels else 0
         p = plan(s, n, per_ch)
         if d_out is None:
-            d_out = torch.zeros((n_streams, p.n_sectors, p.sector_size), dtype=torch.uint8, device=d_frames.device)
+            d_out = _lib.new_tensor(stream, d_frames.device, (n_streams, p.n_sectors, p.sector_size), torch.uint8, 0)
         assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_out.is_contiguous() and tuple(d_out.shape) == (n_streams, p.n_sectors, p.sector_size)
-        st = stream if stream is not None else torch.cuda.current_stream(d_frames.device)
+        st = _lib.launch_stream(stream, d_frames.device)
         rc = _bind().psxhip_str_encode_device(self._h, C.byref(s), n_streams, d_frames.data_ptr(), d_frames.stride(0), n,
                                               d_pcm.data_ptr() if d_pcm is not None and d_pcm.numel() else None,
                                               d_pcm.stride(0) if d_pcm is not None else 0, per_ch, d_out.data_ptr(),

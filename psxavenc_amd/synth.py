@@ -20,7 +20,7 @@ def frames_device(w, h, seed, first, n, amp, device=0, out=None):
     L = _bind()
     dev = torch.device("cuda", device)
     if out is None:
-        out = torch.empty((n, w * h * 3 // 2), dtype=torch.uint8, device=dev)
+        out = _lib.new_tensor(None, dev, (n, w * h * 3 // 2), torch.uint8)
     st = torch.cuda.current_stream(dev)
     _lib.check(L.psxhip_synth_frames_device(device, out.data_ptr(), out.stride(0), w, h, seed, first, n, amp, st.cuda_stream))
     return out
@@ -30,7 +30,7 @@ def pcm_device(seed, chain, first, n, kind, device=0, out=None, pitch=1):
     L = _bind()
     dev = torch.device("cuda", device)
     if out is None:
-        out = torch.zeros(n * pitch, dtype=torch.int16, device=dev)
+        out = _lib.new_tensor(None, dev, (n * pitch,), torch.int16, 0)
     st = torch.cuda.current_stream(dev)
     _lib.check(L.psxhip_synth_pcm_device(device, out.data_ptr(), seed, chain, first, n, kind, pitch, st.cuda_stream))
     return out
