@@ -240,6 +240,58 @@ int psxhip_mdec_sse_device(int device, const uint8_t *d_a, const uint8_t *d_b, s
 /* revision of the decoder's kernels (profiles are keyed by it) */
 const char *psxhip_mdec_decode_kernel_rev(void);
 
+/* ---------------------------------------------------------------- display back-end: NV21 -> RGB ---- */
+
+/* The decoder's last stage: NV21 frames, as the reconstruct kernel writes them, to pixels that can be shown -- 24-bit RGB, RGBX, or
+ * the PlayStation frame buffer's 15-bit pixels, which is what the MDEC itself hands out.  It is the inverse of the front-end's
+ * RGB24 -> NV21 for video, as the ADPCM decoder is for audio.  The arithmetic is this library's own, in integers ("psxhip display
+ * v1"; >> is arithmetic), and the kernel is held to it bit for bit:
+ *   chroma  replicate (default): pixel (x, y) takes chroma sample (x >> 1, y >> 1), as the MDEC does.
+ *           PSXHIP_DISPLAY_CHROMA_BILINEAR: centre siting, per channel on the bytes: kx = x >> 1, fx = kx - 1 (even x) or kx + 1
+ *           (odd x), ky and fy likewise from y, fx and fy clamped to the plane;
+ *           v = (9 c[ky][kx] + 3 c[ky][fx] + 3 c[fy][kx] + c[fy][fx] + 8) >> 4 -- one rounding, not two passes.
+ *   matrix  BT.601 full range, cr = Cr - 128, cb = Cb - 128, each result clamped to 0 .. 255:
+ *           R = (65536 Y + 91881 cr + 32768) >> 16
+ *           G = (65536 Y - 22553 cb - 46802 cr + 32768) >> 16
+ *           B = (65536 Y + 116130 cb + 32768) >> 16
+ *   RGB555  c5 = c8 >> 3, or with PSXHIP_DISPLAY_DITHER c5 = clamp(c8 + D[y & 3][x & 3], 0, 255) >> 3, the PlayStation GPU's
+ *           table D = {-4, 0, -3, 1}, {2, -2, 3, -1}, {-3, 1, -4, 0}, {3, -1, 2, -2}; the pixel is the little-endian 16-bit word
+ *           r5 | g5 << 5 | b5 << 10 | m << 15, m = 1 with PSXHIP_DISPLAY_MASK_BIT. */
+enum {
+	PSXHIP_OUT_RGB24 = 0,         /* bytes R, G, B (the scaler's PSXHIP_PIX_RGB24): 3 * width bytes a row */
+	PSXHIP_OUT_RGBX32 = 1,        /* bytes R, G, B, 255: 4 * width */
+	PSXHIP_OUT_RGB555 = 2         /* 16-bit pixels: 2 * width */
+};
+enum {
+	PSXHIP_DISPLAY_CHROMA_BILINEAR = 1,
+	PSXHIP_DISPLAY_DITHER = 2,    /* PSXHIP_OUT_RGB555 only */
+	PSXHIP_DISPLAY_MASK_BIT = 4   /* PSXHIP_OUT_RGB555 only */
+};
+
+/* bytes of one row of pixels; 0 on a bad format */
+size_t psxhip_display_row_bytes(int out_format, int width);
+/* Convert n_frames NV21 frames (frame i at d_frames + i*frame_stride; width, height multiples of 16 in 16 .. 1024).  Picture i
+ * starts at d_dst + i*dst_stride, its row y at + y*dst_pitch; dst_pitch >= the row bytes, dst_stride >= (height - 1)*dst_pitch + the
+ * row bytes.  Only the row bytes of each row are written: what lies between rows and between pictures keeps its contents, so a
+ * picture can be placed inside a larger surface.  d_frames, frame_stride, d_dst, dst_pitch and dst_stride are 4-byte aligned; d_dst
+ * must not overlap d_frames.  With d_decoded (may be NULL; the decoder's records) a frame whose status is not PSXHIP_DEC_OK is
+ * skipped and its picture keeps its contents.  PSXHIP_DISPLAY_DITHER or PSXHIP_DISPLAY_MASK_BIT with another format than
+ * PSXHIP_OUT_RGB555, or an unknown option bit, is PSXHIP_EINVAL.  Asynchronous on `stream`. */
+int psxhip_display_convert_device(int device, const uint8_t *d_frames, size_t frame_stride, int width, int height, int n_frames,
+                                  const psxhip_mdec_decoded_t *d_decoded, int out_format, uint32_t options,
+                                  uint8_t *d_dst, size_t dst_pitch, size_t dst_stride, void *stream);
+/* Same, host buffers, frames and pictures back to back: H2D, kernel, D2H, synchronise. */
+int psxhip_display_convert_host(int device, const uint8_t *frames, int width, int height, int n_frames, int out_format,
+                                uint32_t options, uint8_t *dst);
+/* psxhip_mdec_decode_frames_device followed by the conversion, gated by d_decoded: bitstreams in, pictures out, on the caller's
+ * stream.  The NV21 frames pass through a workspace the context owns (grown on demand); nothing is read back.  The picture of a
+ * frame that does not parse keeps its contents. */
+int psxhip_mdec_decode_display_device(psxhip_mdec_decoder_t *dec, const uint8_t *d_bs, size_t bs_stride, const int32_t *d_bs_sizes,
+                                      int uniform_size, int n_frames, psxhip_mdec_decoded_t *d_decoded, int out_format,
+                                      uint32_t options, uint8_t *d_dst, size_t dst_pitch, size_t dst_stride, void *stream);
+/* revision of the display kernels (profiles are keyed by it) */
+const char *psxhip_display_kernel_rev(void);
+
 /* ---------------------------------------------------------------- SPU / XA ADPCM ----------- */
 
 /* carried state of one channel: the last two DECODED samples (libpsxav/adpcm.c:135-136).  The

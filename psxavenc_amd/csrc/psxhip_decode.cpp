@@ -1,6 +1,6 @@
 // psxhip_decode.cpp -- host side of the MDEC decoder (psxhip_mdec_decoder_*, psxhip_mdec_decode_frames_*, psxhip_mdec_sse_device;
 // include/psxav_hip.h): argument checks, the context's workspace and staging buffers, the launches
-// (mdec_decode_kernels.hip).
+// (mdec_decode_kernels.hip); and psxhip_mdec_decode_display_device, the decoder followed by the display back-end (section 18).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -9,11 +9,13 @@
 #include "device_buffer.h"
 #include "host_layout.h"
 #include "psxhip_decode_internal.h"
+#include "psxhip_display_internal.h"
 #include "psxhip_internal.h"
 
 struct psxhip_mdec_decoder {
     int device, width, height, nblk, wrap;
     DeviceBuffer ws;                  // levels of a call that wants pixels only
+    DeviceBuffer nv21;                // decode_display_device: the frames between the reconstruction and the conversion
     DeviceBuffer stage;               // decode_frames_host: bitstreams, sizes, results, pixels
     DeviceBuffer stage_levels;
 };
@@ -86,6 +88,34 @@ extern "C" int psxhip_mdec_decode_frames_device(psxhip_mdec_decoder_t* dec, cons
         rj.n_frames = n_frames; rj.width = dec->width; rj.height = dec->height;
         HIP_TRY(psxhip_mdec_reconstruct_launch(&rj, stream), PSXHIP_EDEVICE);
     }
+    return PSXHIP_OK;
+}
+
+extern "C" int psxhip_mdec_decode_display_device(psxhip_mdec_decoder_t* dec, const uint8_t* d_bs, size_t bs_stride,
+                                                 const int32_t* d_bs_sizes, int uniform_size, int n_frames,
+                                                 psxhip_mdec_decoded_t* d_decoded, int out_format, uint32_t options, uint8_t* d_dst,
+                                                 size_t dst_pitch, size_t dst_stride, void* stream) {
+    if (!dec || n_frames < 0 || (n_frames > 0 && (!d_bs || !d_decoded || !d_dst))) {
+        psxhip_set_error("psxhip_mdec_decode_display_device: NULL argument or negative frame count");
+        return PSXHIP_EINVAL;
+    }
+    psxhip_display_job_t j;
+    j.frame_stride = (size_t)dec->width * dec->height * 3 / 2;
+    j.d_decoded = d_decoded; j.d_dst = d_dst; j.dst_pitch = dst_pitch; j.dst_stride = dst_stride;
+    j.width = dec->width; j.height = dec->height; j.n_frames = 0; j.out_format = out_format; j.options = options;
+    j.d_frames = nullptr;                                // the workspace: reserved below, and no buffer of the caller's
+    int rc = psxhip_display_check("psxhip_mdec_decode_display_device", &j, true);
+    if (rc) return rc;
+    if (n_frames == 0) return PSXHIP_OK;
+    HIP_TRY(hipSetDevice(dec->device), PSXHIP_EDEVICE);
+    if ((rc = dec->nv21.reserve((size_t)n_frames * j.frame_stride))) return rc;
+    j.d_frames = dec->nv21.as<uint8_t>();
+    j.n_frames = n_frames;
+    // a frame that does not parse leaves its part of the workspace as it was, and the conversion skips it by the same record
+    rc = psxhip_mdec_decode_frames_device(dec, d_bs, bs_stride, d_bs_sizes, uniform_size, n_frames, nullptr, dec->nv21.as<uint8_t>(),
+                                          j.frame_stride, d_decoded, stream);
+    if (rc) return rc;
+    HIP_TRY(psxhip_display_launch(&j, stream), PSXHIP_EDEVICE);
     return PSXHIP_OK;
 }
 

@@ -97,6 +97,29 @@ class MdecDecoder:
             d_decoded.data_ptr(), st.cuda_stream))
         return d_levels, d_frames, d_decoded
 
+    def decode_display_device(self, d_bs, sizes, out_format=0, options=0, d_decoded=None, d_dst=None, dst_pitch=None, stream=None):
+        """psxhip_mdec_decode_display_device: decode_frames_device followed by display.convert_device, gated by the records; the
+        NV21 frames stay in the context's workspace.  d_bs, sizes, d_decoded as decode_frames_device takes them; out_format,
+        options, d_dst, dst_pitch as display.convert_device does.  Returns (d_dst (n, height, dst_pitch) uint8, d_decoded (n, 4));
+        the picture of a frame that does not parse keeps its contents (zeros in a tensor made here).  Asynchronous on the stream."""
+        from . import display
+        assert torch is not None and d_bs.is_cuda and d_bs.dtype == torch.uint8 and d_bs.dim() == 2
+        n = d_bs.shape[0]
+        if isinstance(sizes, int):
+            sizes_p, uniform = None, sizes
+        else:
+            assert sizes.is_cuda and sizes.dtype == torch.int32 and sizes.numel() == n and sizes.is_contiguous()
+            sizes_p, uniform = sizes.data_ptr(), 0
+        if d_decoded is None:
+            d_decoded = _lib.new_tensor(stream, d_bs.device, (n, 4), torch.int32, 0)
+        assert d_decoded.dtype == torch.int32 and d_decoded.is_contiguous() and d_decoded.numel() == n * 4
+        d_dst = display.picture_tensor(stream, d_bs.device, n, self.video_height, out_format, self.video_width, d_dst, dst_pitch)
+        st = _lib.launch_stream(stream, d_bs.device)
+        _lib.check(display._bind().psxhip_mdec_decode_display_device(
+            self._h, d_bs.data_ptr(), d_bs.stride(0), sizes_p, uniform, n, d_decoded.data_ptr(), out_format, options, d_dst.data_ptr(),
+            d_dst.stride(1), d_dst.stride(0), st.cuda_stream))
+        return d_dst, d_decoded
+
     def decode_frames_host(self, bs, sizes, levels=True, frames=True):
         """bs: (n, stride) uint8 host array; sizes: int or int32 sequence.  Returns (levels | None, frames | None, decoded (n, 4))."""
         bs = np.ascontiguousarray(bs, dtype=np.uint8)
