@@ -1082,6 +1082,105 @@ int psxhip_scaler_convert_host(psxhip_scaler_t *s, const uint8_t *src, int n_fra
  * the number of output positions, *taps per position; fills left[n] / coef[n * taps] when both are given (cap elements) */
 int psxhip_scaler_filter(const psxhip_scaler_t *s, int which, int *taps, int32_t *left, int16_t *coef, int cap);
 
+/* ---------------------------------------------------------------- picture ingest: decoder formats -> the scaler's input ---- */
+
+/* The step in front of the scaler: the pictures a video decoder produces -- planar, semi-planar or packed, 8 or 10 bits, padded
+ * rows, any of five colour matrices in limited or full range -- to one of the scaler's two inputs, tightly packed at the source's
+ * size, on the device.  The reference hands libswscale the decoder's pix_fmt and the stream's matrix and range
+ * (psxavenc/decoding.c:287-311); the arithmetic here is this library's own, in integers ("psxhip ingest v1", DESIGN.md section 19;
+ * >> is arithmetic), and the kernel is held to it bit for bit -- PARITY WITH LIBSWSCALE IS UNPINNED, as for the scaler.
+ *
+ * A source picture is up to three planes, each at a byte offset inside the picture with a pitch in bytes (>= the row's bytes); planes
+ * must not overlap.  Chroma planes of a subsampled axis have ceil(n / 2) samples.  16-bit formats are little-endian words and need
+ * even offsets, pitches, source address and src_stride. */
+enum {
+	PSXHIP_SRC_YUV420P = 0,     /* planes Y, Cb, Cr */
+	PSXHIP_SRC_YUV422P = 1,
+	PSXHIP_SRC_YUV444P = 2,
+	PSXHIP_SRC_NV12 = 3,        /* planes Y, CbCr pairs */
+	PSXHIP_SRC_NV21 = 4,        /* planes Y, CrCb pairs */
+	PSXHIP_SRC_YUYV422 = 5,     /* one plane, Y Cb Y Cr; even width */
+	PSXHIP_SRC_UYVY422 = 6,     /* one plane, Cb Y Cr Y; even width */
+	PSXHIP_SRC_YUV420P10 = 7,   /* 16-bit words, the value in the low 10 bits (higher bits are masked off) */
+	PSXHIP_SRC_YUV422P10 = 8,
+	PSXHIP_SRC_YUV444P10 = 9,
+	PSXHIP_SRC_P010 = 10,       /* NV12 of 16-bit words, the value = word >> 6 */
+	PSXHIP_SRC_GRAY8 = 11,
+	PSXHIP_SRC_RGB24 = 12,      /* one plane, R G B */
+	PSXHIP_SRC_BGR24 = 13,
+	PSXHIP_SRC_RGBA32 = 14,     /* R G B A, alpha dropped */
+	PSXHIP_SRC_BGRA32 = 15
+};
+/* the source's matrix (YUV and grey sources): Kr, Kb = 0.299, 0.114 (also BT.470BG, SMPTE170M) / 0.2126, 0.0722 / 0.212, 0.087 /
+ * 0.30, 0.11 / 0.2627, 0.0593 (non-constant luminance) */
+enum {
+	PSXHIP_MATRIX_BT601 = 0,
+	PSXHIP_MATRIX_BT709 = 1,
+	PSXHIP_MATRIX_SMPTE240M = 2,
+	PSXHIP_MATRIX_FCC = 3,
+	PSXHIP_MATRIX_BT2020_NCL = 4
+};
+enum {
+	PSXHIP_INGEST_CHROMA_BILINEAR = 1   /* RGB24 output: centre-sited mix of subsampled chroma instead of replication */
+};
+typedef struct {
+	size_t offset;      /* of the plane's first byte inside a picture */
+	size_t pitch;       /* bytes from a row to the next */
+} psxhip_ingest_plane_t;
+typedef struct psxhip_ingest psxhip_ingest_t;
+
+/* Checks the source and computes the matrix; no device is touched before a conversion (`device` is the one conversions run on), so
+ * the rules and psxhip_ingest_matrix hold on a machine without one.  planes[n_planes]: as many as the format has.  matrix and
+ * full_range (0 = limited) apply to YUV and grey sources.  out_format:
+ *   PSXHIP_PIX_RGB24    every source; width and height may be odd.  Subsampled chroma is replicated (x >> 1, y >> 1), or with
+ *                       PSXHIP_INGEST_CHROMA_BILINEAR mixed as the display back-end mixes it, at the source's depth: 4:2:0
+ *                       (9 near + 3 far_x + 3 far_y + far_xy + 8) >> 4, 4:2:2 (3 near + far + 2) >> 2, the far sample on the pixel's
+ *                       own side, clamped to the plane.  Then, full range out,
+ *                         c = clamp((cy (Y - yoff) + cu (Cb - coff) + cv (Cr - coff) + 32768) >> 16, 0, 255)
+ *                       with (cu, cv) = (0, rv) for R, (gu, gv) for G, (bu, 0) for B: 16 fractional bits, each the round-half-up of
+ *                       the exact rational (psxhip_ingest_matrix).  Grey: R = G = B from the luma term.  RGB sources: a byte shuffle.
+ *   PSXHIP_PIX_YUV420P  YUV and grey sources whose matrix is BT.601, even width and height: samples are copied, 10-bit ones as
+ *                       min(255, (v + 2) >> 2); 4:2:2 and 4:4:4 chroma is box-averaged to 4:2:0 with one rounding, depth reduction
+ *                       included; grey gets chroma 128.  The range is not touched: hand full_range to psxhip_scaler_create.
+ * PSXHIP_EINVAL, with the rule in psxhip_last_error(), for anything else. */
+int psxhip_ingest_create(psxhip_ingest_t **g, int device, int src_format, int width, int height, const psxhip_ingest_plane_t *planes,
+                         int n_planes, int matrix, int full_range, int out_format, uint32_t options);
+void psxhip_ingest_destroy(psxhip_ingest_t *g);
+/* bytes of one output picture (the scaler's psxhip_scaler_source_bytes), and from a source picture's first byte to the end of its
+ * last plane (the least src_stride) */
+size_t psxhip_ingest_output_bytes(const psxhip_ingest_t *g);
+size_t psxhip_ingest_source_bytes(const psxhip_ingest_t *g);
+/* out: cy, rv, gu, gv, bu, yoff, coff (all 0 for an RGB source) */
+int psxhip_ingest_matrix(const psxhip_ingest_t *g, int32_t out[7]);
+/* Output picture i (at d_out + i*out_stride, psxhip_ingest_output_bytes of it written, the rest up to out_stride kept) is made from
+ * source picture d_src_index[i] (at d_src + that*src_stride); d_src_index NULL: from source picture i.  A repeated index reads the
+ * same source again, an index that does not occur is never read, and a negative index (or one >= n_src) leaves that output picture
+ * as it was.  Only the sources' sample bytes are read.  n_out = 0 touches nothing.  d_out must not overlap d_src.  Asynchronous
+ * on `stream`; the call needs no temporary memory. */
+int psxhip_ingest_convert_device(psxhip_ingest_t *g, const uint8_t *d_src, size_t src_stride, int n_src, const int32_t *d_src_index,
+                                 int n_out, uint8_t *d_out, size_t out_stride, void *stream);
+/* Same, host buffers (src_index too): H2D, kernel, D2H, synchronise. */
+int psxhip_ingest_convert_host(psxhip_ingest_t *g, const uint8_t *src, size_t src_stride, int n_src, const int32_t *src_index,
+                               int n_out, uint8_t *out, size_t out_stride);
+/* revision of the ingest kernels (profiles are keyed by it) */
+const char *psxhip_ingest_kernel_rev(void);
+
+/* The planners: no device.
+ * recommend: PSXHIP_PIX_YUV420P when psxhip_ingest_create would accept it for this source (the cheap path), else PSXHIP_PIX_RGB24;
+ * PSXHIP_EINVAL for an unknown format. */
+int psxhip_ingest_recommend(int src_format, int matrix, int width, int height);
+/* decoding.c:275-285: the target size (max_w x max_h, multiples of 16 in 16 .. 1024) reduced to the source's aspect ratio, in the
+ * reference's double-precision expressions: src_ratio < dst_ratio ? w = ((int)round(h * src_ratio) + 15) & ~15
+ * : h = ((int)round(w / src_ratio) + 15) & ~15; unchanged with ignore_aspect (FLAG_BS_IGNORE_ASPECT).  PSXHIP_EINVAL when a side
+ * comes out 0 or above its maximum. */
+int psxhip_ingest_fit(int src_w, int src_h, int max_w, int max_h, int ignore_aspect, int *dst_w, int *dst_h);
+/* decoding.c:412-461: decoded pictures with time stamps pts[n] (in tb_num / tb_den seconds) to frames at fps_num / fps_den.  With
+ * p = (double)pts * tb_num / tb_den and step = fps_den / fps_num: a picture with p < next after the first kept one is dropped; the
+ * first kept one sets next = p, later ones next += step; then max(0, (int)ceil((p - next) / step)) repeats of the last kept picture
+ * come out, each with next += step, and then the picture itself.  Fills out_index (cap entries at most) with the picture of each
+ * output frame -- what d_src_index takes -- and returns the number of output frames, also when cap is too small. */
+int psxhip_ingest_pace(const int64_t *pts, int n, int tb_num, int tb_den, int fps_num, int fps_den, int32_t *out_index, int cap);
+
 /* ---------------------------------------------------------------- audio front-end: resample + remix ---- */
 
 /* What the reference leaves to FFmpeg's libswresample (psxavenc/decoding.c:215-254: swr_alloc_set_opts2 to S16 at the target

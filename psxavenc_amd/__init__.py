@@ -11,6 +11,8 @@ BS_CODEC_V2, BS_CODEC_V3, BS_CODEC_V3DC = 0, 1, 2   # bs_codec_t, psxavenc/args.
 from .decode import MdecDecoder, psnr  # noqa: E402,F401
 from . import display  # noqa: E402,F401  (display.kernel_rev(): the revision of the display back-end's kernels)
 from .display import DISPLAY_CHROMA_BILINEAR, DISPLAY_DITHER, DISPLAY_MASK_BIT, OUT_RGB24, OUT_RGB555, OUT_RGBX32  # noqa: E402,F401
+from . import ingest  # noqa: E402,F401  (ingest.kernel_rev(): the revision of the picture ingest's kernels)
+from .ingest import Ingest, ingest_scale_device  # noqa: E402,F401
 from . import adpcm_decode  # noqa: E402,F401  (adpcm_decode.kernel_rev(): the revision of the ADPCM decoder's kernels)
 from .adpcm_decode import (adpcm_sse, decode_chains_chunked, decode_chains_device, snr_db, spu_decode_streams,  # noqa: E402,F401
                            xa_decode_streams, xa_disassemble)
