@@ -7,12 +7,19 @@ import numpy as np
 
 import ingest_ref as R
 
-# the sizes at which the kernel can go wrong: a run of eight pixels and two rows per lane, so 1 .. 7 pixels left over at the right
-# edge, one lane, more than one lane, more than one wavefront; 2 mod 4 widths start every other packed output row off a dword
+# the sizes at which the kernel can go wrong: a run of eight pixels and two rows per lane (a picture has ceil(w / 8) ceil(h / 2)
+# lanes), so 1 .. 7 pixels left over at the right edge, one lane, more than one lane; 2 mod 4 widths start every other packed output
+# row off a dword.  All of these stay inside one wavefront of 64 lanes: the largest are 127x5 (48 lanes), 66x10 (45), 130x4 (34) and
+# 258x2 (33)
 EVEN_SIZES = [(2, 2), (6, 4), (18, 2), (34, 6), (66, 10), (130, 4), (258, 2)]
 ODD_SIZES = [(1, 1), (3, 3), (5, 7), (33, 1), (65, 3), (127, 5)]          # RGB24 output only
 # ... and sizes whose rows are whole runs on dwords, which the sizes above never are: the kernel's dword loads and stores
 WHOLE_SIZES = [(8, 2), (16, 4), (24, 6), (64, 4)]
+# ... and sizes of more than one wavefront and more than one workgroup of 256 lanes, shown on their own (wide_sizes_for): 130x10 is
+# 85 lanes, two wavefronts whose bilinear rows meet across the seam; 512x6 is 192, whole dwords and a wavefront per row; 522x10 is
+# 330, two workgroups, rows that start off a dword and a tail of 74 lanes; 2050x2 is 257, a second workgroup of one lane; 517x5 is
+# 195 and odd (RGB24 output only, not for packed formats)
+WIDE_SIZES = [(130, 10), (512, 6), (522, 10), (2050, 2), (517, 5)]
 MATRICES = (R.BT601, R.BT709, R.BT2020)
 PADS = (1, 3, 13)
 OFFSETS = (0, 1, 2, 3)
@@ -21,6 +28,14 @@ OFFSETS = (0, 1, 2, 3)
 def sizes_for(fmt, out_format):
     sizes = EVEN_SIZES + WHOLE_SIZES + (ODD_SIZES if out_format == R.OUT_RGB24 else [])
     return [s for s in sizes if not (fmt in R.PACKED and s[0] % 2)]
+
+
+def wide_sizes_for(fmt, out_format):
+    return [s for s in WIDE_SIZES if not ((s[0] | s[1]) & 1 and (out_format != R.OUT_RGB24 or fmt in R.PACKED))]
+
+
+def lanes_of(w, h):
+    return ((w + 7) // 8) * ((h + 1) // 2)
 
 
 def settings_for(fmt):

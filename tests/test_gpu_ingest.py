@@ -78,6 +78,29 @@ def test_every_setting_over_the_corpus(ingest, fmt):
             assert torch.equal(d_src.cpu(), torch.from_numpy(src)), "the source changed"
 
 
+@pytest.mark.parametrize("fmt", R.ALL_FORMATS, ids=R.NAMES)
+def test_every_setting_at_sizes_of_several_wavefronts_and_workgroups(ingest, fmt):
+    """the sizes the matrix above stays below (it ends at 48 lanes, inside one wavefront): two wavefronts whose bilinear rows meet across
+    the seam, a wavefront per row of whole dwords, two workgroups with a ragged tail, a second workgroup of one lane, and an odd size"""
+    import torch
+    unit = 2 if fmt in R.TEN_BIT else 1
+    lanes = []
+    for out_format in (R.OUT_RGB24, R.OUT_YUV420P):
+        settings = [s for s in K.settings_for(fmt) if s[2] == out_format]
+        for w, h in K.wide_sizes_for(fmt, out_format) if settings else []:
+            lanes.append(K.lanes_of(w, h))
+            planes, size = R.layout(fmt, w, h)
+            src, _ = K.pictures(fmt, w, h, planes, size + 3 * unit, seed=23)
+            d_src = _to_device(src)
+            for m, full, out, opt in settings:
+                g = ingest.Ingest(fmt, w, h, planes, m, full, out, opt)
+                got = g.convert_device(d_src)
+                _same(got, R.convert(src, fmt, w, h, planes, m, full, out, opt), _what(fmt, w, h, m, full, out, opt))
+                g.close()
+            assert torch.equal(d_src.cpu(), torch.from_numpy(src)), "the source changed"
+    assert sorted(set(lanes)) == ([85, 192, 257, 330] if fmt in R.PACKED else [85, 192, 195, 257, 330])
+
+
 # ---------------------------------------------------------------------------------------------------------------- placement
 @pytest.mark.parametrize("fmt", R.ALL_FORMATS, ids=R.NAMES)
 def test_padded_pitches_shifted_planes_and_untouched_bytes(ingest, fmt):
