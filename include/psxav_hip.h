@@ -1011,7 +1011,8 @@ void psxhip_disc_reader_destroy(psxhip_disc_reader_t *reader);
 
 /* d_image: n_sectors x 2352 bytes.  d_sector_table (optional) [n_sectors], d_track_counts [n_tracks] (every track's sectors, dropped
  * ones included; may be NULL when n_tracks is 0) and *d_summary are overwritten; all device memory.  Refused (PSXHIP_EINVAL, before
- * any device call): a pointer or stride not 4-byte aligned, stride < sector_size, a sector size other than the three, file or channel
+ * any device call): a pointer or stride not 4-byte aligned, d_summary not 8-byte aligned (it holds a 64-bit counter the kernels add to
+ * atomically), stride < sector_size, a sector size other than the three, file or channel
  * number out of range, capacity < 0, a track with capacity > 0 and no buffer, more than PSXHIP_DISC_MAX_SOURCES tracks, n_sectors < 0
  * or >= 2^31, a track buffer that overlaps the image or another track's.  Asynchronous on `stream`; nothing is read back;
  * n_sectors == 0 is fine. */

@@ -345,10 +345,16 @@ __global__ __launch_bounds__(64) void adpcm_sse_kernel(const psxhip_adpcm_sse_jo
 }  // namespace
 
 extern "C" hipError_t psxhip_adpcm_decode_launch(const psxhip_adpcm_decode_job_t* j, int verify, int bits, void* stream) {
-    const auto kernel = verify ? (bits == 4 ? adpcm_decode_kernel<true, 4> : adpcm_decode_kernel<true, 8>)
-                               : (bits == 4 ? adpcm_decode_kernel<false, 4> : adpcm_decode_kernel<false, 8>);
-    void* args[] = {(void*)j};
-    return hipLaunchKernel((const void*)kernel, dim3((unsigned)((j->n_items + 63) / 64)), dim3(64), args, 0, (hipStream_t)stream);
+    const dim3 grid((unsigned)((j->n_items + 63) / 64));
+    hipStream_t st = (hipStream_t)stream;
+    if (verify) {
+        if (bits == 4) hipLaunchKernelGGL((adpcm_decode_kernel<true, 4>), grid, dim3(64), 0, st, *j);
+        else hipLaunchKernelGGL((adpcm_decode_kernel<true, 8>), grid, dim3(64), 0, st, *j);
+    } else {
+        if (bits == 4) hipLaunchKernelGGL((adpcm_decode_kernel<false, 4>), grid, dim3(64), 0, st, *j);
+        else hipLaunchKernelGGL((adpcm_decode_kernel<false, 8>), grid, dim3(64), 0, st, *j);
+    }
+    return hipGetLastError();
 }
 
 extern "C" hipError_t psxhip_adpcm_decode_final_launch(const int32_t* last_chunk, const unsigned long long* chunk_end, int n_chains,

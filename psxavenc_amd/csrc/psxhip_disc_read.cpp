@@ -46,8 +46,8 @@ int check_call(const char* who, const uint8_t* d_image, int64_t n_sectors, const
     const int rc = check_tracks(who, n_sectors, tracks, n_tracks);
     if (rc) return rc;
     if ((n_sectors > 0 && !d_image) || !d_summary || (n_tracks > 0 && !d_counts) || misaligned(d_image) || misaligned(d_table) ||
-        misaligned(d_counts) || misaligned(d_summary)) {
-        psxhip_set_error("%s: d_image, d_track_counts or d_summary NULL, or a pointer not 4-byte aligned", who);
+        misaligned(d_counts) || ((uintptr_t)d_summary & 7) != 0) {      // (n_corrections takes a 64-bit atomic add)
+        psxhip_set_error("%s: d_image, d_track_counts or d_summary NULL, a pointer not 4-byte aligned, or d_summary not 8-byte aligned", who);
         return PSXHIP_EINVAL;
     }
     const uintptr_t i0 = (uintptr_t)d_image, i1 = i0 + (size_t)n_sectors * 2352;
@@ -196,7 +196,9 @@ extern "C" int psxhip_disc_read_host(psxhip_disc_reader_t* reader, const uint8_t
     // only the slots that were written travel back
     for (int t = 0; t < n_tracks; t++) {
         const psxhip_disc_track_t& T = tracks[t];
-        const size_t rows = (size_t)(track_counts[t] < T.capacity ? track_counts[t] : T.capacity);
+        int32_t count;                     // (track_counts is the caller's host memory: no alignment rule)
+        memcpy(&count, (const uint8_t*)track_counts + (size_t)t * 4, sizeof count);
+        const size_t rows = (size_t)(count < T.capacity ? count : T.capacity);
         if (rows > 0)
             HIP_TRY(hipMemcpy2DAsync(T.sectors, (size_t)T.stride, d + at[t], (size_t)T.sector_size, (size_t)T.sector_size, rows,
                                      hipMemcpyDeviceToHost, st), PSXHIP_EDEVICE);

@@ -1,14 +1,18 @@
 // tests/cpu/hip_lanes/hip/hip_runtime.h -- TEST INFRASTRUCTURE, NOT HIP: a stand-in of this name for the host compiler, so that the
-// text of a barrier-free kernel file (psxavenc_amd/csrc/{ingest,display,strspu,synth}_kernels.hip) compiles unchanged with g++ and
-// runs lane by lane on the CPU under -fsanitize=address,undefined (tests/cpu/*_lanes.cpp; the include path puts this folder first).
-// It holds what those four files use and no more: the function qualifiers as empty words, dim3 and the four index variables, uint4 /
-// int4, the byte permute the kernels pack with, and a hipLaunchKernelGGL that calls the kernel once per lane.
+// text of a kernel file compiles unchanged with g++ and runs on the CPU under -fsanitize=address,undefined (tests/cpu/*_lanes.cpp;
+// the include path puts this folder first).  It has two forms.
 //
-// A lane runs to its end before the next one starts, in the order the program chose (hip_lanes::order): ascending, descending, or a
-// seeded shuffle of all (workgroup, lane) pairs of the launch.  A kernel whose lanes do not talk to each other gives the same bytes
-// in all three.  Nothing here can hold a lane at a barrier: kernels with __syncthreads, LDS or cross-lane operations do not compile
-// against this file (none of those words is defined).  hip_lanes::run_grid is the one place that walks lanes; a barrier would go
-// there, by running a workgroup's lanes as coroutines that are resumed round by round.
+// Without HIP_LANES_WAVES it holds what the barrier-free kernel files (psxavenc_amd/csrc/{ingest,display,strspu,synth}_kernels.hip)
+// use and no more: the function qualifiers as empty words, dim3 and the four index variables, uint4 / int4, the byte permute the
+// kernels pack with, and a hipLaunchKernelGGL that calls the kernel once per lane.  A lane runs to its end before the next one
+// starts, in the order the program chose (hip_lanes::order): ascending, descending, or a seeded shuffle of all (workgroup, lane)
+// pairs of the launch.  A kernel whose lanes do not talk to each other gives the same bytes in all three.
+//
+// With HIP_LANES_WAVES defined in front of the kernel file's text (the reader side: {disc_read,str_demux,strspu_demux,mdec_decode,
+// adpcm_decode}_kernels.hip) the launch goes through the wavefront model of hip_lanes_waves.h instead: a workgroup's lanes are
+// fibers that are resumed round by round, held at __syncthreads and at every cross-lane operation, with LDS, atomics, __constant__
+// and the small CPU "device" of hip_lanes_device.h that the modules' host layer needs.  That file says what the model guarantees,
+// what it reports and what it cannot see.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -106,5 +110,12 @@ void launch(Kernel kernel, dim3 grid, dim3 block, const Args&... args) {
 }  // namespace hip_lanes
 
 // (dynamic LDS bytes and the stream are taken and ignored: the launch has run when this returns)
+#ifdef HIP_LANES_WAVES
+#include "../hip_lanes_device.h"
+#include "../hip_lanes_waves.h"
+#define hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, ...) \
+    do { (void)(lds_bytes); (void)(stream); hip_lanes::launch_waves(kernel, grid, block, __VA_ARGS__); } while (0)
+#else
 #define hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, ...) \
     do { (void)(lds_bytes); (void)(stream); hip_lanes::launch(kernel, grid, block, __VA_ARGS__); } while (0)
+#endif

@@ -82,6 +82,7 @@ def test_every_refusal_of_the_specification(handle):
     assert discread.kernel_rev() == "disc-rd-k1.0"
     bad_calls = [
         dict(image=IMAGE + 2), dict(table=TABLE + 1), dict(counts=COUNTS + 2), dict(summary=SUMMARY + 3),      # a misaligned pointer
+        dict(summary=SUMMARY + 4),                                                                              # (the summary: 8-byte aligned)
         dict(tracks=[_track(sectors=P + 2)]), dict(tracks=[_track(stride=2338)]),                               # ... or stride
         dict(tracks=[_track(stride=2332)]), dict(tracks=[_track(size=2352, stride=2048)]),                      # stride < sector_size
         dict(tracks=[_track(size=2340, stride=2340)]), dict(tracks=[_track(size=0)]), dict(tracks=[_track(size=2324, stride=2336)]),
