@@ -105,6 +105,10 @@ static inline void fill_interleaved_chains(psxhip_adpcm_chain_t* chains, int32_t
         }
 }
 
+// the alignment every device pointer of the readers' entry points needs at the least: 4 bytes
+static inline bool misaligned(uintptr_t p) { return (p & 3) != 0; }
+static inline bool misaligned(const void* p) { return misaligned((uintptr_t)p); }
+
 // carves one allocation into 256-byte aligned parts: take() returns the part's offset, `end` is the size so far
 struct BumpOffsets {
     size_t end = 0;

@@ -12,8 +12,6 @@
 
 namespace {
 
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
-
 // the layout and the sources against the rules that need no pointer; fills the per-slot ranks and per-source slot counts and returns
 // the sectors of the whole schedule, or PSXHIP_EINVAL with the text set
 int64_t plan(const char* who, const psxhip_disc_layout_t* L, const psxhip_disc_source_t* src, int n_sources, int* count, uint8_t* rank) {

@@ -20,8 +20,6 @@ struct psxhip_disc_reader {
 
 namespace {
 
-bool misaligned(const void* p) { return ((uintptr_t)p & 3) != 0; }
-
 // the rules of the track list that need no pointer
 int check_tracks(const char* who, int64_t n_sectors, const psxhip_disc_track_t* tracks, int n_tracks) {
     if (n_sectors < 0 || n_sectors > 0x7FFFFFFFll || n_tracks < 0 || n_tracks > PSXHIP_DISC_MAX_SOURCES || (n_tracks > 0 && !tracks)) {

@@ -68,6 +68,41 @@ def _ptr(t):
     return t.data_ptr() if t is not None else None
 
 
+def _out(t, stream, dev, shape, dtype, padded=False):
+    """An output tensor of a device call: a new zeroed one on the stream when t is None, else t held to shape and dtype -- contiguous,
+    or, for the tensors whose stride over streams may be padded, with rows that lie back to back within a stream."""
+    if t is None:
+        return _lib.new_tensor(stream, dev, shape, dtype, 0)
+    assert t.dtype == dtype and tuple(t.shape) == tuple(shape), (t.dtype, tuple(t.shape), shape)
+    if padded:
+        assert t.stride(2) == 1 and (shape[1] == 0 or t.stride(1) == shape[2]), "rows lie back to back: a row's pitch is its length"
+    else:
+        assert t.is_contiguous()
+    return t
+
+
+def _sectors_3d(d_sectors, ssz):
+    """the sectors of a device call as (S, n_sectors, sector size): one stream may come without its first dimension"""
+    assert torch is not None and d_sectors.is_cuda and d_sectors.dtype == torch.uint8
+    if d_sectors.dim() == 2:
+        d_sectors = d_sectors.unsqueeze(0)
+    n = d_sectors.shape[1]
+    assert d_sectors.shape[2] == ssz and d_sectors.stride(2) == 1 and (n == 0 or d_sectors.stride(1) == ssz)
+    return d_sectors, d_sectors.shape[0], n
+
+
+def _host_arrays(s, sectors, ssz, max_frames, frames, want_frames):
+    """what both host readers take and fill: the sectors as (n, sector size), then frames (the caller's, zeros, or None), info,
+    decoded, summary"""
+    sectors = np.ascontiguousarray(sectors, dtype=np.uint8).reshape(-1, ssz)
+    frame_bytes = s.video_width * s.video_height * 3 // 2
+    if want_frames and frames is None:
+        frames = np.zeros((max_frames, frame_bytes), np.uint8)
+    if frames is not None:
+        assert frames.dtype == np.uint8 and frames.flags.c_contiguous and frames.shape == (max_frames, frame_bytes)
+    return sectors, frames, np.zeros((max_frames, 8), np.int32), np.zeros((max_frames, 4), np.int32), np.zeros(8, np.int32)
+
+
 def spu_deinterleave_device(d_in, lane_bytes, channels, lane_offset=0, d_src_chunk=None, n_chunks=None, d_units=None, stream=None):
     """psxhip_spu_deinterleave_device.  d_in: uint8 CUDA tensor (S, chunks, chunk_stride), or (chunks, chunk_stride) for one stream; its
     strides over streams and chunks may be padded.  Chunk k is row d_src_chunk[k] of d_in (int32 CUDA tensor (n_chunks,), a negative
@@ -121,33 +156,20 @@ class StrReader:
         [INFO_FIELDS], d_xa (S, xa_capacity, sector size) uint8 (xa_capacity None: n_sectors), d_table (S, n_sectors, 4) int32 [kind,
         frame, index, flags] (table=False: none), d_summary (S, 8) int32 [SUMMARY_FIELDS].  Returns a dict of those tensors under the
         names bs, sizes, info, xa, table, summary; asynchronous on the stream."""
-        assert torch is not None and d_sectors.is_cuda and d_sectors.dtype == torch.uint8
-        if d_sectors.dim() == 2:
-            d_sectors = d_sectors.unsqueeze(0)
         ssz = SECTOR_SIZE[s.format]
-        S, n = d_sectors.shape[0], d_sectors.shape[1]
-        assert d_sectors.shape[2] == ssz and d_sectors.stride(2) == 1 and (n == 0 or d_sectors.stride(1) == ssz)
+        d_sectors, S, n = _sectors_3d(d_sectors, ssz)
         dev = d_sectors.device
         if xa_capacity is None:
             xa_capacity = n
-        if d_bs is None:
-            d_bs = _lib.new_tensor(stream, dev, (S, max_frames, bs_stride), torch.uint8, 0)
-        if d_sizes is None:
-            d_sizes = _lib.new_tensor(stream, dev, (S, max_frames), torch.int32, 0)
-        if d_info is None:
-            d_info = _lib.new_tensor(stream, dev, (S, max_frames, 8), torch.int32, 0)
-        if d_xa is None:
-            d_xa = _lib.new_tensor(stream, dev, (S, xa_capacity, ssz), torch.uint8, 0)
-        if d_table is None and table:
-            d_table = _lib.new_tensor(stream, dev, (S, n, 4), torch.int32, 0)
-        if d_summary is None:
-            d_summary = _lib.new_tensor(stream, dev, (S, 8), torch.int32, 0)
-        assert d_bs.dtype == torch.uint8 and tuple(d_bs.shape) == (S, max_frames, bs_stride) and d_bs.stride(2) == 1
-        assert d_xa.dtype == torch.uint8 and tuple(d_xa.shape) == (S, xa_capacity, ssz) and (xa_capacity == 0 or d_xa.stride(1) == ssz)
-        for t, shape in ((d_sizes, (S, max_frames)), (d_info, (S, max_frames, 8)), (d_summary, (S, 8))) + (((d_table, (S, n, 4)),) if d_table is not None else ()):
-            assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
+        # a row's pitch is bs_stride: room behind the last whole chunk is the row's margin
+        d_bs = _out(d_bs, stream, dev, (S, max_frames, bs_stride), torch.uint8, padded=True)
+        d_sizes = _out(d_sizes, stream, dev, (S, max_frames), torch.int32)
+        d_info = _out(d_info, stream, dev, (S, max_frames, 8), torch.int32)
+        d_xa = _out(d_xa, stream, dev, (S, xa_capacity, ssz), torch.uint8, padded=True)
+        if d_table is not None or table:
+            d_table = _out(d_table, stream, dev, (S, n, 4), torch.int32)
+        d_summary = _out(d_summary, stream, dev, (S, 8), torch.int32)
         st = _lib.launch_stream(stream, dev)
-        assert max_frames == 0 or d_bs.stride(1) == bs_stride, "a row's pitch is bs_stride: room behind the last whole chunk is the row's margin"
         _lib.check(_bind().psxhip_str_demux_device(
             self._h, C.byref(s), S, d_sectors.data_ptr(), d_sectors.stride(0) if S > 1 else 0, n, int(first_frame), max_frames,
             d_bs.data_ptr(), bs_stride, d_bs.stride(0) if S > 1 else 0, d_sizes.data_ptr(), d_info.data_ptr(), d_xa.data_ptr(), xa_capacity,
@@ -160,23 +182,15 @@ class StrReader:
         want_frames=False: no pictures).  pcm_sectors: XA sectors to decode at the most (None: all of the stream's; 0: no audio).
         Returns dict(frames, info (max_frames, 8) int32 [INFO_FIELDS], decoded (max_frames, 4) int32 [status, quant scale, version, bits
         consumed], pcm int16 (interleaved L,R when stereo), xa_status int32 per decoded XA sector, summary (8,) int32 [SUMMARY_FIELDS])."""
-        ssz = SECTOR_SIZE[s.format]
-        sectors = np.ascontiguousarray(sectors, dtype=np.uint8).reshape(-1, ssz)
+        sectors, frames, info, decoded, summary = _host_arrays(s, sectors, SECTOR_SIZE[s.format], max_frames, frames, want_frames)
         n = sectors.shape[0]
-        if want_frames and frames is None:
-            frames = np.zeros((max_frames, s.video_width * s.video_height * 3 // 2), np.uint8)
-        if frames is not None:
-            assert frames.dtype == np.uint8 and frames.flags.c_contiguous and frames.shape == (max_frames, s.video_width * s.video_height * 3 // 2)
-        info = np.zeros((max_frames, 8), np.int32)
-        decoded = np.zeros((max_frames, 4), np.int32)
-        summary = np.zeros(8, np.int32)
         per_sector = 4032 if s.audio_bit_depth == 4 else 2016
         cap = n if pcm_sectors is None else int(pcm_sectors)
         pcm = np.zeros(max(cap, 1) * per_sector, np.int16)
         xa_status = np.zeros(max(cap, 1), np.int32)
         rc = _bind().psxhip_str_read_host(self._h, C.byref(s), sectors.ctypes.data if n else None, n, int(first_frame), max_frames,
-                                          frames.ctypes.data if frames is not None else None, info.ctypes.data, decoded.ctypes.data,
-                                          pcm.ctypes.data if cap else None, cap * per_sector, xa_status.ctypes.data, summary.ctypes.data)
+                                          frames.ctypes.data if frames is not None else None, info.ctypes.data, decoded.ctypes.data, pcm.ctypes.data if cap else None, cap * per_sector, xa_status.ctypes.data,
+                                          summary.ctypes.data)
         if rc < 0:
             _lib.check(rc)
         ch = max(1, s.audio_channels)
@@ -192,39 +206,20 @@ class StrReader:
         (audio_capacity None: n_sectors), d_chunk_info (S, audio_capacity, 8) int32 [CHUNK_FIELDS], d_audio_summary (S, 4) int32
         [AUDIO_SUMMARY_FIELDS].  Returns a dict of those tensors under the names bs, sizes, info, units, chunk_info, table, summary,
         audio_summary; asynchronous on the stream."""
-        assert torch is not None and d_sectors.is_cuda and d_sectors.dtype == torch.uint8
-        if d_sectors.dim() == 2:
-            d_sectors = d_sectors.unsqueeze(0)
-        ssz = STRSPU_SECTOR
-        S, n = d_sectors.shape[0], d_sectors.shape[1]
-        assert d_sectors.shape[2] == ssz and d_sectors.stride(2) == 1 and (n == 0 or d_sectors.stride(1) == ssz)
+        d_sectors, S, n = _sectors_3d(d_sectors, STRSPU_SECTOR)
         dev = d_sectors.device
         if audio_capacity is None:
             audio_capacity = n
-        if d_bs is None:
-            d_bs = _lib.new_tensor(stream, dev, (S, max_frames, bs_stride), torch.uint8, 0)
-        if d_sizes is None:
-            d_sizes = _lib.new_tensor(stream, dev, (S, max_frames), torch.int32, 0)
-        if d_info is None:
-            d_info = _lib.new_tensor(stream, dev, (S, max_frames, 8), torch.int32, 0)
-        if d_units is None:
-            d_units = _lib.new_tensor(stream, dev, (S, audio_capacity * 126, 16), torch.uint8, 0)
-        if d_chunk_info is None:
-            d_chunk_info = _lib.new_tensor(stream, dev, (S, audio_capacity, 8), torch.int32, 0)
-        if d_table is None and table:
-            d_table = _lib.new_tensor(stream, dev, (S, n, 4), torch.int32, 0)
-        if d_summary is None:
-            d_summary = _lib.new_tensor(stream, dev, (S, 8), torch.int32, 0)
-        if d_audio_summary is None:
-            d_audio_summary = _lib.new_tensor(stream, dev, (S, 4), torch.int32, 0)
-        assert d_bs.dtype == torch.uint8 and tuple(d_bs.shape) == (S, max_frames, bs_stride) and d_bs.stride(2) == 1
-        assert d_units.dtype == torch.uint8 and tuple(d_units.shape) == (S, audio_capacity * 126, 16) and d_units.stride(2) == 1
-        assert audio_capacity == 0 or d_units.stride(1) == 16
-        for t, shape in ((d_sizes, (S, max_frames)), (d_info, (S, max_frames, 8)), (d_summary, (S, 8)), (d_audio_summary, (S, 4)),
-                         (d_chunk_info, (S, audio_capacity, 8))) + (((d_table, (S, n, 4)),) if d_table is not None else ()):
-            assert t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()
+        d_bs = _out(d_bs, stream, dev, (S, max_frames, bs_stride), torch.uint8, padded=True)
+        d_sizes = _out(d_sizes, stream, dev, (S, max_frames), torch.int32)
+        d_info = _out(d_info, stream, dev, (S, max_frames, 8), torch.int32)
+        d_units = _out(d_units, stream, dev, (S, audio_capacity * 126, 16), torch.uint8, padded=True)
+        d_chunk_info = _out(d_chunk_info, stream, dev, (S, audio_capacity, 8), torch.int32)
+        if d_table is not None or table:
+            d_table = _out(d_table, stream, dev, (S, n, 4), torch.int32)
+        d_summary = _out(d_summary, stream, dev, (S, 8), torch.int32)
+        d_audio_summary = _out(d_audio_summary, stream, dev, (S, 4), torch.int32)
         st = _lib.launch_stream(stream, dev)
-        assert max_frames == 0 or d_bs.stride(1) == bs_stride, "a row's pitch is bs_stride: room behind the last whole chunk is the row's margin"
         _lib.check(_bind().psxhip_strspu_demux_device(
             self._h, C.byref(s), S, d_sectors.data_ptr(), d_sectors.stride(0) if S > 1 else 0, n, int(first_frame), max_frames,
             d_bs.data_ptr(), bs_stride, d_bs.stride(0) if S > 1 else 0, d_sizes.data_ptr(), d_info.data_ptr(),
@@ -239,26 +234,19 @@ class StrReader:
         pcm_capacity: int16 elements of room for PCM (None: room for a chunk per sector; 0: no audio, pcm NULL).  Returns dict(frames,
         info, decoded as read()'s, pcm int16 (interleaved L,R when stereo), chunk_info (chunks taken apart, 8) int32 [CHUNK_FIELDS],
         summary (8,) int32 [SUMMARY_FIELDS], audio_summary (4,) int32 [AUDIO_SUMMARY_FIELDS])."""
-        sectors = np.ascontiguousarray(sectors, dtype=np.uint8).reshape(-1, STRSPU_SECTOR)
+        sectors, frames, info, decoded, summary = _host_arrays(s, sectors, STRSPU_SECTOR, max_frames, frames, want_frames)
         n = sectors.shape[0]
-        if want_frames and frames is None:
-            frames = np.zeros((max_frames, s.video_width * s.video_height * 3 // 2), np.uint8)
-        if frames is not None:
-            assert frames.dtype == np.uint8 and frames.flags.c_contiguous and frames.shape == (max_frames, s.video_width * s.video_height * 3 // 2)
-        info = np.zeros((max_frames, 8), np.int32)
-        decoded = np.zeros((max_frames, 4), np.int32)
-        summary = np.zeros(8, np.int32)
         audio_summary = np.zeros(4, np.int32)
         ch = s.audio_channels
         cap = n * 126 * 28 if pcm_capacity is None else int(pcm_capacity)
         pcm = np.zeros(max(cap, 1), np.int16)
+        # the chunk records the library writes: the chunks the PCM buffer holds (reader_plan.cpp: strspu_read_capacity)
         d = 0 if s.strspu_options & 0x20000 else 1
-        held = min(n, (cap // (28 * ch) + d) // (126 // ch)) if ch and cap else 0
+        held = min(n, (cap // (28 * ch) + d) // (126 // ch), STRSPU_MAX_CHUNKS // 28) if ch and cap else 0
         chunk_info = np.zeros((max(held, 1), 8), np.int32)
         rc = _bind().psxhip_strspu_read_host(self._h, C.byref(s), sectors.ctypes.data if n else None, n, int(first_frame), max_frames,
-                                             frames.ctypes.data if frames is not None else None, info.ctypes.data, decoded.ctypes.data,
-                                             pcm.ctypes.data if cap else None, cap, chunk_info.ctypes.data, summary.ctypes.data,
-                                             audio_summary.ctypes.data)
+                                             frames.ctypes.data if frames is not None else None, info.ctypes.data, decoded.ctypes.data, pcm.ctypes.data if cap else None, cap, chunk_info.ctypes.data,
+                                             summary.ctypes.data, audio_summary.ctypes.data)
         if rc < 0:
             _lib.check(rc)
         return dict(frames=frames, info=info, decoded=decoded, pcm=pcm[:rc * max(1, ch)], chunk_info=chunk_info[:held], summary=summary,

@@ -29,6 +29,7 @@
 #include "../../psxavenc_amd/csrc/str_demux_kernels.hip"
 #include "../../psxavenc_amd/csrc/strspu_demux_kernels.hip"
 #include "../../psxavenc_amd/csrc/psxhip_str_demux.cpp"
+#include "../../psxavenc_amd/csrc/reader_plan.cpp"
 #include "../../psxavenc_amd/csrc/str_plan.cpp"
 
 // stand-ins for what the _host entry points compose the readers with; never reached from this program

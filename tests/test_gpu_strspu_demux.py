@@ -402,3 +402,44 @@ def test_read_strspu_decodes_a_missing_chunk_as_silence():
     d = 0 if s.strspu_options & M.NO_LEADING_DUMMY else 1
     assert np.array_equal(got["pcm"], X.decode_lanes(R.lane_streams(units, 2), d)) and got["chunk_info"][1, 1] == R.MISSING
     assert not got["pcm"].reshape(-1, 2)[28 * (63 - d):28 * (126 - d)].any() and got["pcm"].reshape(-1, 2)[28 * (126 - d):].any()
+
+
+def test_one_reader_strcd_then_strspu_then_strcd(monkeypatch):
+    """both _host readers on ONE fresh handle in turns -- about 8 sectors and 1 frame of an STRCD stream, the smallest STRSPU case (one
+    audio chunk), the STRCD piece again: they share the handle's staging buffer and its keyed BS decoder, and the STRCD pictures are
+    64 x 48 where the STRSPU stream's are 48 x 32, so the decoder is rebuilt for the second and again for the third call.  Every call
+    against the expectation of its own file: _expected_read (tests/test_gpu_str_demux.py) and composition"""
+    import test_gpu_str_demux as T
+    from psxavenc_amd import MdecDecoder, StrReader, strmux
+    monkeypatch.setattr(T, "W", 64)          # clean_stream and _expected_read build pictures of the module's size
+    monkeypatch.setattr(T, "H", 48)
+    s7, _, d7, p7, _ = T.clean_stream(7, 0, 2, 15, 4, seed=11)          # (a seed no other test muxes: the cache is keyed without the size)
+    cd = d7.cpu().numpy()[:8]
+    assert cd.shape[0] == 8 and (s7.video_width, s7.video_height) == (64, 48) != (W, H)
+    stride = int(strmux.frame_budgets(s7, 0, p7.n_frames_encoded).max())
+    dec = MdecDecoder(64, 48, dc_wrap=False, device=0)
+    want, px, decoded, pcm, status = T._expected_read(s7, dec, cd, 1, stride)
+    dec.close()
+    assert want["summary"][0] > 0 and pcm.size > 0
+    case = X.EDGES[1]
+    ns, frames, _, sectors, rows, K, budgets = X.stream(case)
+    s8, d8, _, _ = muxed(case)
+    assert K == 1
+    comp = composition(s8, d8, frames.shape[0], int(budgets.max()), K)
+    reader = StrReader(0)
+    for turn in ("strcd", "strspu", "strcd"):
+        if turn == "strcd":
+            got = reader.read(s7, cd, 1, first_frame=1, frames=np.full((1, 64 * 48 * 3 // 2), 0x55, np.uint8))
+            assert np.array_equal(got["info"], want["info"]) and np.array_equal(got["summary"], want["summary"])
+            assert np.array_equal(got["decoded"], decoded) and np.array_equal(got["frames"], px)
+            assert got["pcm"].size == pcm.size and np.array_equal(got["pcm"], pcm)
+            assert np.array_equal(got["xa_status"], status) and not status.any()
+        else:
+            got = reader.read_strspu(s8, sectors, frames.shape[0], first_frame=1)
+            assert np.array_equal(got["frames"], comp["frames"]) and np.array_equal(got["decoded"], comp["decoded"])
+            assert np.array_equal(got["info"], comp["out"]["info"][0].cpu().numpy())
+            assert np.array_equal(got["summary"], comp["out"]["summary"][0].cpu().numpy())
+            assert np.array_equal(got["audio_summary"], comp["out"]["audio_summary"][0].cpu().numpy())
+            assert got["pcm"].size > 0 and np.array_equal(got["pcm"], comp["pcm"]) and np.array_equal(got["pcm"], X.expected_pcm(case))
+            assert np.array_equal(got["chunk_info"][:K], comp["out"]["chunk_info"][0].cpu().numpy())
+    reader.close()
