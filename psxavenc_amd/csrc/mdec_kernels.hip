@@ -696,8 +696,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
     uint32_t* clist = (uint32_t*)tileT;                                // code list of a macroblock (aliases both tiles)
 
     // Per-lane constants of the pixel gather (seven registers each lane would otherwise carry -- or spill to scratch -- for
-    // the whole kernel) and the scan-order table: the same for every wavefront and every frame, they live in LDS tables and
-    // are read where they are used.
+    // the whole kernel) and the scan-order table: the same for every wavefront and every frame, they live in LDS tables.  The
+    // pilot reads them where it uses them; a pass of the 12-wavefront shapes reads the gather's two entries once and holds them
+    // across its macroblock loop.
     {
         if (tid < 64) {
             L.qzz[tid] = pro_qzz;
@@ -1146,14 +1147,22 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         // =====================================================================================
         float cf[6];            // this lane's coefficient of each block of the current macroblock, as float; lane 0 holds 0
         uint2 plo = make_uint2(0, 0), phi = make_uint2(0, 0);
+        // The 12-wavefront shapes hold the gather's per-lane tables in registers across a pass's macroblock loop (mdec-k3.11); the
+        // 16-wavefront shapes read them from LDS in every macroblock, as before: no measured workload runs them, and with the tables
+        // held their macroblocks ran far enough ahead of the checkpoint's judge for tests/test_gpu_mdec_sampled_count.py's model
+        // of it (at most three macroblocks per wavefront behind the mark) to fail on one or two frames in 32 (NOTEBOOK).
+        constexpr bool kHoldTables = WAVES == kWavesSmall;
 
-        auto fetch_at = [&](uint32_t row, uint32_t col) {       // row = fy * 8 W, col = fx * 16
+        auto fetch_entry = [&](const uint4& tp, uint32_t row, uint32_t col) {       // tp = tab_pix[lane], row = fy * 8 W, col = fx * 16
             // 32-bit offsets from the (wave-uniform) frame pointer; the macroblock row's offset is scalar arithmetic, a lane
             // only shifts it (a macroblock row is 8 W bytes of chroma, 16 W of luma)
-            const uint4 tp = L.tab_pix[lane];
             const uint32_t o_lo = tp.x + (row << tp.z) + col, o_hi = o_lo + tp.y;
             plo = *(const uint2*)(frame + o_lo);
             phi = *(const uint2*)(frame + o_hi);
+        };
+        auto fetch_at = [&](uint32_t row, uint32_t col) {
+            const uint4 tp = L.tab_pix[lane];
+            fetch_entry(tp, row, col);
         };
         auto fetch = [&](int fx, int fy) { fetch_at((uint32_t)fy * (uint32_t)(8 * W), (uint32_t)fx * 16u); };
         // the lane's 8 pixels as bytes (b_lo: p0..p3, b_hi: p4..p7) from what fetch() left in (plo, phi)
@@ -1166,9 +1175,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         // registers the permutes have just read.  (Issued under `if (there is a next one)`, and hoisted above the permutes by
         // the scheduler, the loads needed a second set of four registers and 8 v_mov per macroblock to shuttle between the sets
         // -- 3 % of the loop's VALU instructions.)
-        auto fetch_behind = [&](uint32_t row, uint32_t col, uint32_t& b_lo, uint32_t& b_hi) {      // row = fy * 8 W, col = fx * 16 (what the pass table holds)
+        auto fetch_behind = [&](const uint4& held, uint32_t row, uint32_t col, uint32_t& b_lo, uint32_t& b_hi) {      // held: tab_pix[lane] where the pass holds it; row = fy * 8 W, col = fx * 16 (what the pass table holds)
             asm volatile("" : "+v"(b_lo), "+v"(b_hi));
-            const uint4 tp = L.tab_pix[lane];
+            uint4 tp = held;
+            if constexpr (!kHoldTables) tp = L.tab_pix[lane];
             uint32_t o_lo = tp.x + (row << tp.z) + col;
             asm volatile("" : "+v"(o_lo) : "v"(b_lo), "v"(b_hi));      // the address is "made from" the bytes: the loads stay behind the permutes
             const uint32_t o_hi = o_lo + tp.y;
@@ -1296,6 +1306,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         group_sync(1);
         if (L.scalars[S_PILOT_GUESS] == 0) {
         float cfp[kPilotPerWave][6];
+        // (Zeroed where the pilot starts: unset, the select below kept the previous frame's six values alive across the whole pass
+        //  loop -- two of them spilled to scratch as soon as the loop held the gather's tables in registers.)
+        if constexpr (kHoldTables) {
+#pragma unroll
+            for (int b = 0; b < 6; b++) cf[b] = 0.0f;
+        }
 #pragma unroll
         for (int i = 0; i < kPilotPerWave; i++) {
             const int pi = wid + i * kWavesPerGroup;
@@ -1432,7 +1448,18 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             int cur_t = wid, nxt_t = wid + kWavesPerGroup;
             uint2 cur_o = order_at(cur_t);
             uint2 nxt_o = order_at(nxt_t);
-            fetch_at(cur_o.x & 0x7FFFFFFFu, cur_o.y & 0xFFFFu);
+            // The gather's per-lane tables in registers for the whole pass: read once here, pinned (the compiler neither re-reads nor
+            // re-derives them), they cost seven registers across the macroblock loop and save every macroblock the two LDS round
+            // trips it used to start with -- tab_sel ahead of the permutes, tab_pix ahead of the next macroblock's address.
+            uint4 g_sel = make_uint4(0, 0, 0, 0), g_pix = make_uint4(0, 0, 0, 0);
+            if constexpr (kHoldTables) {
+                g_sel = L.tab_sel[lane];
+                g_pix = L.tab_pix[lane];
+                asm volatile("" : "+v"(g_sel.x), "+v"(g_sel.y), "+v"(g_sel.z), "+v"(g_sel.w), "+v"(g_pix.x), "+v"(g_pix.y), "+v"(g_pix.z));
+                fetch_entry(g_pix, cur_o.x & 0x7FFFFFFFu, cur_o.y & 0xFFFFu);
+            } else {
+                fetch_at(cur_o.x & 0x7FFFFFFFu, cur_o.y & 0xFFFFu);
+            }
             const QuantK kc = make_quant(lc.quant, count_scale ? count_scale : 1);
             const QuantK ke = make_quant(lc.quant, emit_scale ? emit_scale : 1);
             // v2: a macroblock is counted while the ticket drawn last is below this (0: the pass does not count; kStopCount: until the judge sets that bit)
@@ -1586,10 +1613,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 const uint32_t rec_byte = cur_o.y >> 16;        // 4 * the macroblock's encode-order index: its record's byte offset
                 const int mbe = (int)(rec_byte >> 2);
                 {
-                    const uint4 ts = L.tab_sel[lane];
+                    uint4 ts = g_sel;
+                    if constexpr (!kHoldTables) ts = L.tab_sel[lane];
                     uint32_t b_lo, b_hi;
                     mb_bytes(ts, b_lo, b_hi);
-                    fetch_behind(nxt_o.x & 0x7FFFFFFFu, nxt_o.y & 0xFFFFu, b_lo, b_hi);
+                    fetch_behind(g_pix, nxt_o.x & 0x7FFFFFFFu, nxt_o.y & 0xFFFFu, b_lo, b_hi);
                     if (valid) dct_mb(ts, b_lo, b_hi);
                 }
                 cur_t = nxt_t;

@@ -8,7 +8,7 @@
 #include "mdec_plan.h"
 
 /* bumped with every change to the MDEC kernel: bench.py keys the committed PMC summaries on it (profiles/pmc_index.json) */
-#define PSXHIP_MDEC_KERNEL_REV "mdec-k3.10"
+#define PSXHIP_MDEC_KERNEL_REV "mdec-k3.11"
 /* ... and with every change to the ADPCM kernels (round 4's kernels count as adpcm-k4.0) */
 #define PSXHIP_ADPCM_KERNEL_REV "adpcm-k5.4"
 
