@@ -135,6 +135,41 @@ int psxhip_mdec_encode_frames_host(psxhip_mdec_ctx_t *ctx, const uint8_t *frames
                                    const int32_t *frame_max_sizes, int uniform_max_size, uint8_t *out,
                                    size_t out_stride, psxhip_mdec_result_t *results);
 
+/* Refinement, "psxhip MDEC shed v1" (DESIGN.md section 21).  The encoder's first-fit loop picks the smallest scale N whose stream fits and
+ * leaves unused whatever lies between that stream and the budget.  This call, made AFTER an encode on the same frames, rows and
+ * results, tries every frame with 1 < N < 64 at M = N - 1: AC levels are zeroed in shed steps t = 1 .. 63 * max_magnitude (step t
+ * zeroes every |level| <= m - 1, and every |level| <= m at zig-zag positions >= p, with m = 1 + (t - 1) / 63 and
+ * p = 64 - ((t - 1) % 63 + 1)); t* is the first step whose stream fits the frame's budget by the encoder's own rule; the frame is
+ * refined when the squared error of its AC coefficients against their reconstruction is then below the plain encode's.  A refined
+ * frame's row is what encode_frame_bs would write for the shed levels at scale M (all frame_max_size bytes), and its result matches;
+ * every other frame's row and result stay bit for bit as they were.  The DC is never touched.
+ *   max_magnitude  1 .. 3
+ *   d_refine       (may be NULL) one record per frame
+ * Arguments, alignment rules and the vetting of per-frame budgets are those of psxhip_mdec_encode_frames_device; a frame whose
+ * budget is outside the allowed range is left as it was.  Asynchronous on `stream`, nothing is read back; the call orders `stream`
+ * behind every launch of the context first (as psxhip_mdec_fence does), so it is correct with one or two launch lanes.  The
+ * workspace belongs to the context and grows on demand: calls on one context must be stream-ordered.  Refining rows that were refined
+ * already is the caller's error (the result's scale is no longer the plain encode's).  PSXHIP_EINVAL, with the rule in the error text,
+ * for a call outside these rules. */
+typedef struct {
+	int32_t shed_step;           /* t*, 0 = untouched or declined */
+	int32_t shed_count;          /* AC levels zeroed (0 unless refined) */
+	int64_t d_plain;             /* sum (F - R_N)^2 over the frame's AC coefficients; 0 when untouched or when no step fits */
+	int64_t d_shed;              /* the same against the shed levels at scale M, at t* */
+} psxhip_mdec_refine_t;
+int psxhip_mdec_refine_frames_device(psxhip_mdec_ctx_t *ctx, const uint8_t *d_frames, size_t frame_stride, int n_frames,
+                                     const int32_t *d_frame_max_sizes, int uniform_max_size, int max_magnitude,
+                                     uint8_t *d_out, size_t out_stride, psxhip_mdec_result_t *d_results,
+                                     psxhip_mdec_refine_t *d_refine, void *stream);
+/* psxhip_mdec_encode_frames_host with the refinement between the kernel and the copy back: H2D, encode, refine, D2H, synchronise.
+ * refine: (may be NULL) [n_frames].  A frame the split kernel's watchdog released is encoded again through the frame kernel and
+ * comes back unrefined. */
+int psxhip_mdec_encode_refine_frames_host(psxhip_mdec_ctx_t *ctx, const uint8_t *frames, int n_frames,
+                                          const int32_t *frame_max_sizes, int uniform_max_size, int max_magnitude, uint8_t *out,
+                                          size_t out_stride, psxhip_mdec_result_t *results, psxhip_mdec_refine_t *refine);
+/* revision of the refinement's kernels */
+const char *psxhip_mdec_shed_kernel_rev(void);
+
 /* The 8x8 forward DCT alone, exactly as the frame kernel computes it: blocks = n_blocks * 64 level-shifted samples
  * (-128..127, raster order; what psxavenc/mdec.c:619-633 hands to AVDCT.fdct), coefs = the 64 coefficients per block
  * in raster order (the in-place result of mdec.c:640).  The FDCT is the one piece of the path the reference takes from

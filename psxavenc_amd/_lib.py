@@ -21,6 +21,11 @@ class MdecResult(C.Structure):
                 ("blocks_used", C.c_int32), ("uncomp_hwords_used", C.c_int32)]
 
 
+class MdecRefine(C.Structure):
+    """psxhip_mdec_refine_t (include/psxav_hip.h)"""
+    _fields_ = [("shed_step", C.c_int32), ("shed_count", C.c_int32), ("d_plain", C.c_int64), ("d_shed", C.c_int64)]
+
+
 class AdpcmState(C.Structure):
     _fields_ = [("prev1", C.c_int32), ("prev2", C.c_int32)]
 
@@ -64,6 +69,9 @@ def lib():
     L.psxhip_mdec_destroy.restype = None
     L.psxhip_mdec_encode_frames_device.argtypes = [vp, u8p, sz, i32, vp, i32, u8p, sz, vp, vp]
     L.psxhip_mdec_encode_frames_host.argtypes = [vp, u8p, i32, vp, i32, u8p, sz, vp]
+    L.psxhip_mdec_refine_frames_device.argtypes = [vp, u8p, sz, i32, vp, i32, i32, u8p, sz, vp, vp, vp]
+    L.psxhip_mdec_encode_refine_frames_host.argtypes = [vp, u8p, i32, vp, i32, i32, u8p, sz, vp, vp]
+    L.psxhip_mdec_shed_kernel_rev.restype = C.c_char_p
     _lib = L
     return L
 

@@ -225,6 +225,45 @@ int mdec_host_call_check(int max_frame_size, int n_frames, const int32_t* frame_
     return PSXHIP_OK;
 }
 
+int mdec_refine_call_check(int max_frame_size, size_t frame_bytes, const MdecRefineCall& a) {
+    if (!a.d_frames || !a.d_out || !a.d_results || a.n_frames < 0) {
+        psxhip_set_error("refine_frames_device: NULL argument");
+        return PSXHIP_EINVAL;
+    }
+    if (a.max_magnitude < 1 || a.max_magnitude > 3) {
+        psxhip_set_error("refine_frames_device: max_magnitude %d outside [1, 3]", a.max_magnitude);
+        return PSXHIP_EINVAL;
+    }
+    if (a.frame_stride < frame_bytes || (a.frame_stride & 3) || (a.out_stride & 3) || ((uintptr_t)a.d_frames & 3) || ((uintptr_t)a.d_out & 3)) {
+        psxhip_set_error("refine_frames_device: strides / pointers must be 4-byte aligned and frame_stride >= w*h*3/2");
+        return PSXHIP_EINVAL;
+    }
+    if (!a.per_frame_budgets && (a.uniform_max_size < 8 || a.uniform_max_size > max_frame_size || (size_t)a.uniform_max_size > a.out_stride)) {
+        psxhip_set_error("refine_frames_device: frame_max_size %d outside [8, %d] or larger than out_stride", a.uniform_max_size, max_frame_size);
+        return PSXHIP_EINVAL;
+    }
+    if (a.n_frames > 0xFFFFFF) {
+        psxhip_set_error("refine_frames_device: more than 16 777 215 frames in one call");
+        return PSXHIP_EINVAL;
+    }
+    return PSXHIP_OK;
+}
+
+MdecShedWs mdec_shed_workspace(int n_blocks) {
+    MdecShedWs w;
+    const size_t nb = (size_t)n_blocks;
+    w.acc = 0;
+    w.decision = 13 * 64 * sizeof(int64_t);            // kShedRows rows (mdec_shed_core.h; the kernels assert the number)
+    w.zeroed = w.decision + 64;
+    w.dc_level = w.zeroed;
+    w.dc_code = (w.dc_level + nb * sizeof(int16_t) + 15) & ~(size_t)15;
+    w.block_off = w.dc_code + nb * sizeof(uint32_t);
+    w.stride = (w.block_off + (nb + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
+    return w;
+}
+
+int mdec_shed_analyse_groups(int nmb) { return (nmb + kShedAnalyseMbs - 1) / kShedAnalyseMbs; }
+
 int mdec_chunk_frames(int groups_max, size_t frame_bytes, int n_frames) {
     // chunk: most of a GPU-load of frames -- small enough that a 1000-frame call already pipelines staging, DMA and kernel
     // over three chunks (353 k frames/s against 269 k with 1024-frame chunks), large enough for launches to stay efficient

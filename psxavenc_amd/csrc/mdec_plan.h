@@ -72,6 +72,25 @@ int mdec_host_call_check(int max_frame_size, int n_frames, const int32_t* frame_
 // frames per chunk of the host path, of frame_bytes each
 int mdec_chunk_frames(int groups_max, size_t frame_bytes, int n_frames);
 
+// The refinement (psxhip_mdec_refine_frames_device; mdec_shed_core.h): the call's checks -- those of psxhip_mdec_encode_frames_device, and
+// max_magnitude in 1 .. 3 -- and the per-frame workspace the three kernels share.  PSXHIP_OK, or PSXHIP_EINVAL with the error text set.
+struct MdecRefineCall {
+    const void *d_frames, *d_out, *d_results;
+    size_t frame_stride, out_stride;
+    int n_frames;
+    bool per_frame_budgets;
+    int uniform_max_size, max_magnitude;
+};
+int mdec_refine_call_check(int max_frame_size, size_t frame_bytes, const MdecRefineCall& a);
+// offsets into a frame's workspace, and its size: the sums first (all of [0, zeroed) is zero before the analysis)
+struct MdecShedWs {
+    size_t acc, decision, zeroed, dc_level, dc_code, block_off, stride;
+};
+MdecShedWs mdec_shed_workspace(int n_blocks);
+// macroblocks one workgroup of the analysis takes, and the workgroups per frame
+constexpr int kShedAnalyseMbs = 16;
+int mdec_shed_analyse_groups(int nmb);
+
 // PSXHIP_MDEC_SPLIT_WITHHOLD (tests; mdec_split.inc's header): launches = 0 is off
 struct MdecWithhold {
     int frame = 0, seg = 0, launches = 0, residue = 0;

@@ -16,6 +16,8 @@
 
 #include "device_buffer.h"
 #include "psxhip_internal.h"
+#include "psxhip_shed_internal.h"
+#include "mdec_shed_core.h"
 
 namespace {
 
@@ -36,6 +38,7 @@ struct SplitGate {
 };
 SplitGate g_split_gate[64];
 bool g_tables_ready[64] = {false};
+bool g_shed_tables_ready[64] = {false};      // the refinement's copies (mdec_shed_kernels.hip), made at a device's first refine call
 
 int ensure_device(int device) {
     int n = 0;
@@ -135,6 +138,7 @@ struct __attribute__((visibility("hidden"))) psxhip_mdec_ctx {      // (the hand
         MdecWithhold wh;            // tests (PSXHIP_MDEC_SPLIT_WITHHOLD)
         long long launches = 0;     // split launches of this context so far
     } split;
+    DeviceBuffer d_shed_ws;         // the refinement's per-frame workspaces (psxhip_mdec_refine_frames_device), grown on demand
 };
 
 namespace {
@@ -886,6 +890,121 @@ extern "C" int psxhip_mdec_encode_frames_host_rows(psxhip_mdec_ctx_t* c, const u
             psxhip_set_error("frame %d does not fit %d bytes at any quant scale", i, hc.budget(i));
             return PSXHIP_ENOFIT;
         }
+    return PSXHIP_OK;
+}
+
+// ---- refinement after an encode ("psxhip MDEC shed v1": mdec_shed_core.h, mdec_shed_kernels.hip)
+extern "C" const char* psxhip_mdec_shed_kernel_rev(void) { return PSXHIP_MDEC_SHED_KERNEL_REV; }
+
+namespace {
+constexpr int kShedSliceFrames = 32768;          // frames per launch of the three kernels: bounds their grids and the workspace
+}
+
+extern "C" int psxhip_mdec_refine_frames_device(psxhip_mdec_ctx_t* c, const uint8_t* d_frames, size_t frame_stride, int n_frames,
+                                                const int32_t* d_frame_max_sizes, int uniform_max_size, int max_magnitude,
+                                                uint8_t* d_out, size_t out_stride, psxhip_mdec_result_t* d_results,
+                                                psxhip_mdec_refine_t* d_refine, void* stream) {
+    if (!c) {          // (no context exists without a device)
+        if (psxhip_device_count() <= 0) return psxhip_no_device();
+        psxhip_set_error("refine_frames_device: NULL argument");
+        return PSXHIP_EINVAL;
+    }
+    const MdecRefineCall call = {d_frames, d_out, d_results, frame_stride, out_stride, n_frames, d_frame_max_sizes != nullptr, uniform_max_size, max_magnitude};
+    int rc = mdec_refine_call_check(c->k.max_frame_size, c->frame_bytes, call);
+    if (rc) return rc;
+    if (n_frames == 0) return PSXHIP_OK;
+    HIP_TRY(hipSetDevice(c->device), PSXHIP_EDEVICE);
+    if ((rc = psxhip_mdec_fence(c, stream))) return rc;
+    {
+        std::lock_guard<std::mutex> lk(g_tables_mu);
+        if (!g_shed_tables_ready[c->device]) {
+            HIP_TRY(psxhip_mdec_shed_upload_tables(), PSXHIP_EDEVICE);
+            g_shed_tables_ready[c->device] = true;
+        }
+    }
+    psxhip_mdec_shed_job_t j;
+    memset(&j, 0, sizeof j);
+    j.frame_stride = frame_stride;
+    j.out_stride = out_stride;
+    j.width = c->k.width;
+    j.height = c->k.height;
+    j.codec = c->k.codec;
+    j.nmb = c->nmb;
+    j.uniform_max_size = uniform_max_size;
+    j.max_frame_size = c->k.max_frame_size;
+    j.max_magnitude = max_magnitude;
+    j.groups_per_frame = mdec_shed_analyse_groups(c->nmb);
+    j.ws = mdec_shed_workspace(c->nmb * 6);
+    const int slice = n_frames < kShedSliceFrames ? n_frames : kShedSliceFrames;
+    if ((rc = c->d_shed_ws.reserve((size_t)slice * j.ws.stride))) return rc;
+    j.d_ws = c->d_shed_ws.as<uint8_t>();
+    for (int f0 = 0; f0 < n_frames; f0 += slice) {
+        j.n_frames = n_frames - f0 < slice ? n_frames - f0 : slice;
+        j.d_frames = d_frames + (size_t)f0 * frame_stride;
+        j.d_out = d_out + (size_t)f0 * out_stride;
+        j.d_results = d_results + f0;
+        j.d_refine = d_refine ? d_refine + f0 : nullptr;
+        j.d_frame_max_sizes = d_frame_max_sizes ? d_frame_max_sizes + f0 : nullptr;
+        HIP_TRY(hipMemset2DAsync(j.d_ws, j.ws.stride, 0, j.ws.zeroed, (size_t)j.n_frames, (hipStream_t)stream), PSXHIP_EDEVICE);
+        HIP_TRY(psxhip_mdec_shed_launch(&j, stream), PSXHIP_EDEVICE);
+    }
+    return PSXHIP_OK;
+}
+
+extern "C" int psxhip_mdec_encode_refine_frames_host(psxhip_mdec_ctx_t* c, const uint8_t* frames, int n_frames, const int32_t* frame_max_sizes,
+                                                     int uniform_max_size, int max_magnitude, uint8_t* out, size_t out_stride,
+                                                     psxhip_mdec_result_t* results, psxhip_mdec_refine_t* refine) {
+    if (!c && psxhip_device_count() <= 0) return psxhip_no_device();
+    if (!c || !frames || !out || !results || n_frames < 0) {
+        psxhip_set_error("encode_refine_frames_host: NULL argument");
+        return PSXHIP_EINVAL;
+    }
+    if (max_magnitude < 1 || max_magnitude > 3) {
+        psxhip_set_error("encode_refine_frames_host: max_magnitude %d outside [1, 3]", max_magnitude);
+        return PSXHIP_EINVAL;
+    }
+    if (n_frames == 0) return PSXHIP_OK;
+    HIP_TRY(hipSetDevice(c->device), PSXHIP_EDEVICE);
+    for (int l = 0; l < kLanes; l++)          // (as psxhip_mdec_encode_frames_host_rows: nothing of the caller's device-path launches is left on the lanes)
+        if (c->lanes.stream[l]) {
+            HIP_TRY(hipStreamSynchronize(c->lanes.stream[l]), PSXHIP_EDEVICE);
+            c->lanes.pending[l] = false;
+        }
+    MdecHostCall vetted;
+    int rc = mdec_host_call_check(c->k.max_frame_size, n_frames, frame_max_sizes, uniform_max_size, out_stride, 0, &vetted);
+    if (rc || (rc = c->stream.ensure())) return rc;
+    hipStream_t S = c->stream;
+    const size_t n = (size_t)n_frames;
+    DeviceBuffer d_frames, d_out, d_res, d_sizes, d_ref;
+    if ((rc = d_frames.reserve(n * c->frame_bytes)) || (rc = d_out.reserve(n * vetted.dstride)) || (rc = d_res.reserve(n * sizeof(psxhip_mdec_result_t))) ||
+        (rc = d_ref.reserve(n * sizeof(psxhip_mdec_refine_t))) || (frame_max_sizes && (rc = d_sizes.reserve(n * sizeof(int32_t)))))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(d_frames.p, frames, n * c->frame_bytes, hipMemcpyHostToDevice, S), PSXHIP_EDEVICE);
+    if (frame_max_sizes) HIP_TRY(hipMemcpyAsync(d_sizes.p, frame_max_sizes, n * sizeof(int32_t), hipMemcpyHostToDevice, S), PSXHIP_EDEVICE);
+    if ((rc = psxhip_mdec_encode_frames_device(c, d_frames.as<uint8_t>(), c->frame_bytes, n_frames, d_sizes.as<int32_t>(), uniform_max_size,
+                                               d_out.as<uint8_t>(), vetted.dstride, d_res.as<psxhip_mdec_result_t>(), S)) ||
+        (rc = psxhip_mdec_refine_frames_device(c, d_frames.as<uint8_t>(), c->frame_bytes, n_frames, d_sizes.as<int32_t>(), uniform_max_size, max_magnitude,
+                                               d_out.as<uint8_t>(), vetted.dstride, d_res.as<psxhip_mdec_result_t>(), d_ref.as<psxhip_mdec_refine_t>(), S)))
+        return rc;
+    HIP_TRY(hipMemcpy2DAsync(out, out_stride, d_out.p, vetted.dstride, (size_t)vetted.max_size, n, hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(results, d_res.p, n * sizeof(psxhip_mdec_result_t), hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
+    if (refine) HIP_TRY(hipMemcpyAsync(refine, d_ref.p, n * sizeof(psxhip_mdec_refine_t), hipMemcpyDeviceToHost, S), PSXHIP_EDEVICE);
+    HIP_TRY(hipStreamSynchronize(S), PSXHIP_EDEVICE);
+    for (int l = 0; l < kLanes; l++)
+        if (c->lanes.stream[l]) {
+            HIP_TRY(hipStreamSynchronize(c->lanes.stream[l]), PSXHIP_EDEVICE);
+            c->lanes.pending[l] = false;
+        }
+    for (int i = 0; i < n_frames; i++) {
+        if (results[i].quant_scale == PSXHIP_MDEC_QS_RELEASED &&          // (rare: another process held the CUs) again, through the frame kernel, unrefined
+            (rc = psxhip_mdec_encode_frames_host(c, frames + (size_t)i * c->frame_bytes, 1, frame_max_sizes ? frame_max_sizes + i : nullptr, uniform_max_size,
+                                                 out + (size_t)i * out_stride, out_stride, results + i)) != PSXHIP_OK && rc != PSXHIP_ENOFIT)
+            return rc;
+        if (results[i].quant_scale >= 64) {
+            psxhip_set_error("frame %d does not fit %d bytes at any quant scale", i, frame_max_sizes ? frame_max_sizes[i] : uniform_max_size);
+            return PSXHIP_ENOFIT;
+        }
+    }
     return PSXHIP_OK;
 }
 

@@ -112,6 +112,51 @@ class MdecEncoder:
         _lib.check(rc)
         return d_out, d_results
 
+    # ---- refinement after an encode: "psxhip MDEC shed v1" (include/psxav_hip.h) ------------------
+    def refine_frames_device(self, d_frames, frame_max_sizes, d_out, d_results, max_magnitude=1, d_refine=None, stream=None,
+                             want_refine=True):
+        """psxhip_mdec_refine_frames_device on what encode_frames_device was given and returned: frames whose plain scale N is in
+        2..63 are tried at N - 1 with AC levels of magnitude <= max_magnitude (1..3) shed until they fit; a frame that gains gets a new
+        row and result, every other stays bit for bit.  Returns d_refine, a (n, 3) int64 CUDA tensor -- psxhip_mdec_refine_t: column 0
+        holds shed_step (low 32 bits) and shed_count (high), then d_plain and d_shed; refine_records() unpacks it -- or None with
+        want_refine=False.  Asynchronous on the stream, ordered behind every launch of this encoder; refine rows once only."""
+        assert torch is not None and d_frames.is_cuda and d_frames.dtype == torch.uint8 and d_frames.dim() == 2
+        assert d_out.is_cuda and d_out.dtype == torch.uint8 and d_results.is_cuda and d_results.dtype == torch.int32
+        n = d_frames.shape[0]
+        assert d_out.shape[0] == n and d_results.shape == (n, 4) and d_results.is_contiguous()
+        if isinstance(frame_max_sizes, int):
+            sizes_p, uniform = None, frame_max_sizes
+        else:
+            assert frame_max_sizes.is_cuda and frame_max_sizes.dtype == torch.int32 and frame_max_sizes.shape == (n,)
+            sizes_p, uniform = frame_max_sizes.data_ptr(), 0
+        if d_refine is None and want_refine:
+            d_refine = _lib.new_tensor(stream, d_frames.device, (n, 3), torch.int64, 0)
+        if d_refine is not None:
+            assert d_refine.is_cuda and d_refine.dtype == torch.int64 and d_refine.shape == (n, 3) and d_refine.is_contiguous()
+        st = _lib.launch_stream(stream, d_frames.device)
+        _lib.check(_lib.lib().psxhip_mdec_refine_frames_device(self._h, d_frames.data_ptr(), d_frames.stride(0), n, sizes_p, uniform,
+                                                               int(max_magnitude), d_out.data_ptr(), d_out.stride(0),
+                                                               d_results.data_ptr(), d_refine.data_ptr() if d_refine is not None else None,
+                                                               st.cuda_stream))
+        return d_refine
+
+    def encode_refine_frames_host(self, frames, frame_max_sizes, max_magnitude=1):
+        """psxhip_mdec_encode_refine_frames_host: encode_frames_host with the refinement before the copy back.
+        Returns (out (n, stride) uint8, res (n, 4) int32, refine (n, 4) int64: shed_step, shed_count, d_plain, d_shed)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        n = frames.shape[0]
+        assert frames.shape[1] == self.frame_bytes
+        if np.isscalar(frame_max_sizes):
+            sizes_p, uniform, stride = None, int(frame_max_sizes), int(frame_max_sizes)
+        else:
+            sizes = np.ascontiguousarray(frame_max_sizes, dtype=np.int32)
+            sizes_p, uniform, stride = sizes.ctypes.data, 0, int(sizes.max())
+        out = np.zeros((n, stride), dtype=np.uint8)
+        res = np.zeros((n, 4), dtype=np.int32)
+        rec = np.zeros((n, 3), dtype=np.int64)
+        _lib.check(_lib.lib().psxhip_mdec_encode_refine_frames_host(self._h, frames.ctypes.data, n, sizes_p, uniform, int(max_magnitude),
+                                                                    out.ctypes.data, stride, res.ctypes.data, rec.ctypes.data))
+        return out, res, refine_records(rec)
 
     def encode_batches_device(self, batches, frame_max_size, stream=None):
         """psxhip_mdec_encode_batches_device: several batches, ONE launch.  batches: sequence of (d_frames, d_out, d_results) or
@@ -164,6 +209,17 @@ class MdecBatch(C.Structure):
     """psxhip_mdec_batch_t"""
     _fields_ = [("d_frames", C.c_void_p), ("n_frames", C.c_int32), ("reserved", C.c_int32), ("d_frame_max_sizes", C.c_void_p),
                 ("d_out", C.c_void_p), ("d_results", C.c_void_p)]
+
+
+def refine_records(rec):
+    """(n, 3) int64 as the library writes psxhip_mdec_refine_t (a host array) -> (n, 4) int64: shed_step, shed_count, d_plain, d_shed"""
+    rec = np.ascontiguousarray(rec, dtype=np.int64)
+    head = rec[:, :1].copy().view(np.int32).astype(np.int64)
+    return np.concatenate([head, rec[:, 1:]], axis=1)
+
+
+def shed_kernel_rev():
+    return _lib.lib().psxhip_mdec_shed_kernel_rev().decode()
 
 
 def register_host(a):
