@@ -429,6 +429,46 @@ int psxhip_xa_encode_streams_host(int device, int format, int stereo, int freque
                                   int samples_per_stream, const int32_t *lbas, psxhip_adpcm_state_t *states,
                                   uint8_t *out, int64_t out_stride, int finalize);
 
+/* ---- "psxhip ADPCM beam v1" (DESIGN.md section 22): a delayed decision inside the sound unit ----
+ * The reference's encoder rounds every sample to the nearest code and ignores that a code also moves the predictor for the rest of
+ * the unit.  The beam encoder tries the reference's own (filter, shift) candidates, but inside each keeps up to `beam` paths: path 0
+ * is the reference's greedy one, the others the smallest-error children (codes q0, q0 - 1, q0 + 1 of every kept path) of the step
+ * before.  A candidate's result is its best path, the unit's the first candidate with the smallest error.  Integers only; the rule
+ * is stated in full in DESIGN.md and held bit for bit to tests/adpcm_beam_ref.py.
+ *   beam == 1 is libpsxav/adpcm.c:142-191 bit for bit (the bytes of psxhip_adpcm_encode_chains_device).
+ *   For every unit the winner's squared error is <= the reference encoder's for the same unit FROM THE SAME STATE.  That is a
+ *   guarantee per unit, not per chain: behind the first unit that differs the two encoders carry different states.
+ * The records are those of the plain encoder (PSXHIP_ADPCM_RECORD_SIZE(bits)) and go to the same packers, sector builders and
+ * decoder.  The per-call drop-ins (psx_audio_spu_encode, psx_audio_xa_encode), the STR / STRSPU muxers, psxhip_spu_file_* and the
+ * multi-device calls do not take a beam in this revision. */
+#define PSXHIP_ADPCM_BEAM_MAX_WIDTH 4
+/* The contract of psxhip_adpcm_encode_chains_device (asynchronous on `stream`, d_units' alignment, only the chains' records written).
+ * beam 1 .. 4.  d_unit_err (optional, 4-byte aligned): one uint32_t per record index, the winner's squared error (saturating at
+ * 2^32 - 1, which the winner never reaches), written for the chains' units only.  Anything else is PSXHIP_EINVAL. */
+int psxhip_adpcm_beam_encode_chains_device(int device, const int16_t *d_samples, const psxhip_adpcm_chain_t *d_chains,
+                                           const int32_t *d_unit_base, int n_chains, int filter_count, int bits, int beam,
+                                           psxhip_adpcm_state_t *d_states, uint8_t *d_units, uint32_t *d_unit_err, void *stream);
+/* psxhip_adpcm_encode_chains_chunked with the beam encoder: the same chunk tables and verify passes (the scheme is right for any
+ * unit encoder that is a function of state and samples); the result is the serial beam call's bit for bit.  beam 1 .. 4. */
+int psxhip_adpcm_beam_encode_chains_chunked(int device, const int16_t *d_samples, const psxhip_adpcm_chain_t *chains,
+                                            const int32_t *unit_base, int n_chains, int filter_count, int bits,
+                                            psxhip_adpcm_state_t *d_states, uint8_t *d_units, int beam, int chunk_units,
+                                            int warmup_units, int max_passes, void *stream);
+/* Which unit encoder a session's speculate and verify launches run: 0 the plain one (the default), 1 .. 4 the beam.  Valid before
+ * the session's first run or after psxhip_adpcm_session_reset; otherwise PSXHIP_EINVAL (a session's records come from one encoder). */
+int psxhip_adpcm_session_set_beam(psxhip_adpcm_session_t *session, int beam);
+/* psxhip_spu_encode_streams_host / psxhip_xa_encode_streams_host with the beam encoder (beam 1 .. 4): the same serial / chunked
+ * choice and the same packers. */
+int psxhip_spu_encode_streams_host_beam(int device, const int16_t *samples, int n_streams, int64_t stream_stride,
+                                        int pitch, int samples_per_stream, psxhip_adpcm_state_t *states,
+                                        uint8_t *out, int64_t out_stride, int beam);
+int psxhip_xa_encode_streams_host_beam(int device, int format, int stereo, int frequency, int bits, int file_number,
+                                       int channel_number, const int16_t *samples, int n_streams, int64_t stream_stride,
+                                       int samples_per_stream, const int32_t *lbas, psxhip_adpcm_state_t *states,
+                                       uint8_t *out, int64_t out_stride, int finalize, int beam);
+/* revision of adpcm_beam_kernels.hip */
+const char *psxhip_adpcm_beam_kernel_rev(void);
+
 /* ---------------------------------------------------------------- SPU / XA ADPCM decoder --- */
 
 /* The way back: unit records (or SPU blocks, or XA sectors) -> int16 PCM, and the sums of squared errors of two sample sets per

@@ -16,6 +16,7 @@ PSX_AUDIO_XA_FREQ_SINGLE, PSX_AUDIO_XA_FREQ_DOUBLE = 18900, 37800  # libpsxav.h:
 PSX_AUDIO_SPU_BLOCK_SIZE, PSX_AUDIO_SPU_SAMPLES_PER_BLOCK = 16, 28
 PSX_AUDIO_SPU_LOOP_END, PSX_AUDIO_SPU_LOOP_REPEAT, PSX_AUDIO_SPU_LOOP_START, PSX_AUDIO_SPU_LOOP_TRAP = 1, 3, 6, 5
 RECORD_BYTES = 32          # 8-bit codes (and the upper bound)
+BEAM_MAX = 4               # PSXHIP_ADPCM_BEAM_MAX_WIDTH: "psxhip ADPCM beam v1" (DESIGN.md section 22); beam=0 is the plain encoder
 
 
 def record_bytes(bits):
@@ -32,6 +33,11 @@ def _bind():
     L.psxhip_adpcm_encode_chains_device.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.psxhip_spu_pack_device.argtypes = [i32, vp, i32, vp, vp]
     L.psxhip_xa_assemble_device.argtypes = [i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.psxhip_spu_encode_streams_host_beam.argtypes = L.psxhip_spu_encode_streams_host.argtypes + [i32]
+    L.psxhip_xa_encode_streams_host_beam.argtypes = L.psxhip_xa_encode_streams_host.argtypes + [i32]
+    L.psxhip_adpcm_beam_encode_chains_device.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.psxhip_adpcm_beam_encode_chains_chunked.argtypes = [i32, vp, vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp]
+    L.psxhip_adpcm_session_set_beam.argtypes = [vp, i32]
     return L
 
 
@@ -72,9 +78,10 @@ def spu_get_buffer_size(sample_count):
 
 
 # ---- batched host paths -------------------------------------------------------------------------
-def spu_encode_streams(samples, pitch=1, states=None, sample_count=None, device=0):
+def spu_encode_streams(samples, pitch=1, states=None, sample_count=None, device=0, beam=0):
     """samples: int16 (n_streams, >= sample_count*pitch).  Returns (n_streams, 16*ceil(n/28)) uint8;
-    `states` (n_streams, 2) int32 [prev1, prev2] is updated in place when given."""
+    `states` (n_streams, 2) int32 [prev1, prev2] is updated in place when given.
+    beam: 0 the reference's encoder, 1 .. 4 the beam encoder (psxhip_spu_encode_streams_host_beam)."""
     L = _bind()
     samples = np.ascontiguousarray(samples, dtype=np.int16)
     assert samples.ndim == 2
@@ -83,16 +90,17 @@ def spu_encode_streams(samples, pitch=1, states=None, sample_count=None, device=
     st = np.zeros((n_streams, 2), np.int32) if states is None else states
     assert st.dtype == np.int32 and st.shape == (n_streams, 2) and st.flags.c_contiguous
     out = np.zeros((n_streams, spu_get_buffer_size(n)), np.uint8)
-    rc = L.psxhip_spu_encode_streams_host(device, samples.ctypes.data, n_streams, samples.shape[1], pitch, n, st.ctypes.data,
-                                          out.ctypes.data, out.shape[1])
+    args = (device, samples.ctypes.data, n_streams, samples.shape[1], pitch, n, st.ctypes.data, out.ctypes.data, out.shape[1])
+    rc = L.psxhip_spu_encode_streams_host_beam(*args, beam) if beam else L.psxhip_spu_encode_streams_host(*args)
     if rc < 0:
         _lib.check(rc)
     return out
 
 
-def xa_encode_streams(settings, samples, sample_count, lbas=None, states=None, finalize=False, device=0):
+def xa_encode_streams(settings, samples, sample_count, lbas=None, states=None, finalize=False, device=0, beam=0):
     """samples: int16 (n_streams, >= sample_count * channels), interleaved L,R when stereo.
-    Returns (n_streams, sectors*sector_size) uint8.  states: (n_streams, 2, 2) int32 [[l1,l2],[r1,r2]]."""
+    Returns (n_streams, sectors*sector_size) uint8.  states: (n_streams, 2, 2) int32 [[l1,l2],[r1,r2]].
+    beam: 0 the reference's encoder, 1 .. 4 the beam encoder (psxhip_xa_encode_streams_host_beam)."""
     L = _bind()
     samples = np.ascontiguousarray(samples, dtype=np.int16)
     n_streams = samples.shape[0]
@@ -107,10 +115,10 @@ def xa_encode_streams(settings, samples, sample_count, lbas=None, states=None, f
     sectors = (groups + 17) // 18
     size = sectors * xa_get_buffer_size_per_sector(settings)
     out = np.zeros((n_streams, max(size, 1)), np.uint8)
-    rc = L.psxhip_xa_encode_streams_host(device, settings.format, int(settings.stereo), settings.frequency,
-                                         settings.bits_per_sample, settings.file_number, settings.channel_number,
-                                         samples.ctypes.data, n_streams, samples.shape[1], sample_count, lb.ctypes.data,
-                                         st_dev.ctypes.data, out.ctypes.data, out.shape[1], int(bool(finalize)))
+    args = (device, settings.format, int(settings.stereo), settings.frequency, settings.bits_per_sample, settings.file_number,
+            settings.channel_number, samples.ctypes.data, n_streams, samples.shape[1], sample_count, lb.ctypes.data,
+            st_dev.ctypes.data, out.ctypes.data, out.shape[1], int(bool(finalize)))
+    rc = L.psxhip_xa_encode_streams_host_beam(*args, beam) if beam else L.psxhip_xa_encode_streams_host(*args)
     if rc < 0:
         _lib.check(rc)
     st[:, :ch, :] = st_dev.reshape(n_streams, ch, 2)
@@ -196,13 +204,15 @@ def make_chains(offsets, pitch, limits, n_units, unit_stride=1):
 
 
 def encode_chains_device(d_samples, chains, unit_base, filter_count, bits, d_states=None, d_units=None, chunk_units=0,
-                         warmup_units=16, max_passes=0, stream=None):
+                         warmup_units=16, max_passes=0, stream=None, beam=0, d_unit_err=None):
     """Run the ADPCM search for `chains` (host CHAIN_DTYPE array) over int16 CUDA tensor `d_samples`.
 
     chunk_units == 0: one serial pass per chain (psxhip_adpcm_encode_chains_device, asynchronous).
     chunk_units  > 0: speculate-and-verify along time (psxhip_adpcm_encode_chains_chunked, synchronous).
     Returns (d_units (total_units, record_bytes(bits)) uint8, d_states (n_chains, 2) int32, verify_passes).
-    stream: the stream of the launches (None: the current one); the Python call waits for it either way."""
+    stream: the stream of the launches (None: the current one); the Python call waits for it either way.
+    beam: 0 the reference's encoder, 1 .. 4 the beam encoder (psxhip_adpcm_beam_encode_chains_*); d_unit_err (serial beam call only):
+    a uint32 CUDA tensor with one element per record index that receives the winner's squared error of every unit."""
     import torch
     L = _bind()
     L.psxhip_adpcm_encode_chains_chunked.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
@@ -217,17 +227,27 @@ def encode_chains_device(d_samples, chains, unit_base, filter_count, bits, d_sta
     if d_units is None:
         d_units = _lib.new_tensor(stream, dev, (max(total, 1), record_bytes(bits)), torch.uint8, 0)
     st = _lib.launch_stream(stream, dev).cuda_stream
+    if d_unit_err is not None and (not beam or chunk_units > 0):
+        raise ValueError("d_unit_err goes with the serial beam call")
     if chunk_units > 0:
-        rc = L.psxhip_adpcm_encode_chains_chunked(dev.index or 0, d_samples.data_ptr(), chains.ctypes.data, unit_base.ctypes.data,
-                                                  n, filter_count, bits, d_states.data_ptr(), d_units.data_ptr(), chunk_units,
-                                                  warmup_units, max_passes, st)
+        head = (dev.index or 0, d_samples.data_ptr(), chains.ctypes.data, unit_base.ctypes.data, n, filter_count, bits,
+                d_states.data_ptr(), d_units.data_ptr())
+        if beam:
+            rc = L.psxhip_adpcm_beam_encode_chains_chunked(*head, beam, chunk_units, warmup_units, max_passes, st)
+        else:
+            rc = L.psxhip_adpcm_encode_chains_chunked(*head, chunk_units, warmup_units, max_passes, st)
         if rc < 0:
             _lib.check(rc)
         return d_units, d_states, rc
     d_chains = _lib.to_device(stream, dev, chains.view(np.uint8).reshape(n, CHAIN_DTYPE.itemsize).copy())
     d_base = _lib.to_device(stream, dev, unit_base)
-    _lib.check(L.psxhip_adpcm_encode_chains_device(dev.index or 0, d_samples.data_ptr(), d_chains.data_ptr(), d_base.data_ptr(), n,
-                                                   filter_count, bits, d_states.data_ptr(), d_units.data_ptr(), st))
+    if beam:
+        _lib.check(L.psxhip_adpcm_beam_encode_chains_device(dev.index or 0, d_samples.data_ptr(), d_chains.data_ptr(), d_base.data_ptr(), n,
+                                                            filter_count, bits, beam, d_states.data_ptr(), d_units.data_ptr(),
+                                                            d_unit_err.data_ptr() if d_unit_err is not None else None, st))
+    else:
+        _lib.check(L.psxhip_adpcm_encode_chains_device(dev.index or 0, d_samples.data_ptr(), d_chains.data_ptr(), d_base.data_ptr(), n,
+                                                       filter_count, bits, d_states.data_ptr(), d_units.data_ptr(), st))
     _lib.launch_stream(stream, dev).synchronize()    # d_chains / d_base are temporaries
     return d_units, d_states, 0
 
@@ -284,7 +304,7 @@ class AdpcmSession:
     start states can be corrected later (time-sharding across GPUs, psxavenc_amd/parallel.py)."""
 
     def __init__(self, d_samples, chains, unit_base, filter_count, bits, d_units=None, lead_units=None, chunk_units=128,
-                 warmup_units=32):
+                 warmup_units=32, beam=0):
         import torch
         L = _bind()
         L.psxhip_adpcm_session_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -307,6 +327,13 @@ class AdpcmSession:
                                                  self.n_chains, filter_count, bits, self.d_units.data_ptr(), chunk_units,
                                                  warmup_units, torch.cuda.current_stream(dev).cuda_stream))
         self.passes = 0
+        if beam:
+            self.set_beam(beam)
+
+    def set_beam(self, beam):
+        """which unit encoder the session's launches run: 0 the reference's, 1 .. 4 the beam encoder.  Before the first run or after
+        reset() (psxhip_adpcm_session_set_beam)"""
+        _lib.check(self._L.psxhip_adpcm_session_set_beam(self._h, beam))
 
     def run(self, start_states, known=None, max_passes=0):
         """start_states (n_chains, 2) int32; known (n_chains,) bool/uint8 or None (= all known).

@@ -39,6 +39,35 @@ extern "C" int psxhip_adpcm_encode_chains_device(int device, const int16_t* d_sa
     return PSXHIP_OK;
 }
 
+// "psxhip ADPCM beam v1" (DESIGN.md section 22): the contract of the call above, a beam of 1 .. 4 paths per candidate, and optionally
+// the winner's squared error per record index
+extern "C" int psxhip_adpcm_beam_encode_chains_device(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains,
+                                                      const int32_t* d_unit_base, int n_chains, int filter_count, int bits, int beam,
+                                                      psxhip_adpcm_state_t* d_states, uint8_t* d_units, uint32_t* d_unit_err, void* stream) {
+    if (!d_samples || !d_chains || !d_unit_base || !d_states || !d_units || n_chains < 0 ||
+        (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || beam < 1 || beam > PSXHIP_ADPCM_BEAM_MAX_WIDTH ||
+        units_misaligned(d_units, bits) || ((uintptr_t)d_unit_err & 3)) {
+        psxhip_set_error("adpcm_beam_encode_chains: bad argument (beam 1 .. 4; d_units 16-byte aligned for 4-bit records, 4-byte for 8-bit)");
+        return PSXHIP_EINVAL;
+    }
+    int rc = psxhip_ensure_device(device);
+    if (rc) return rc;
+    if (n_chains == 0) return PSXHIP_OK;
+    psxhip_adpcm_beam_chain_job_t bj;
+    bj.job.samples = d_samples;
+    bj.job.chains = d_chains;
+    bj.job.unit_base = d_unit_base;
+    bj.job.n_chains = n_chains;
+    bj.job.filter_count = filter_count;
+    bj.job.range = bits == 4 ? 12 : 8;
+    bj.job.states = d_states;
+    bj.job.units = d_units;
+    bj.beam = beam;
+    bj.unit_err = d_unit_err;
+    HIP_TRY(psxhip_adpcm_beam_chains_launch(&bj, stream), PSXHIP_EDEVICE);
+    return PSXHIP_OK;
+}
+
 namespace {
 // A session owns one block of device memory.  The one-call entry points (psxhip_adpcm_encode_chains_chunked and the *_host
 // wrappers above it) build and drop a session per call, and a hipMalloc / hipFree pair costs more than encoding a
@@ -78,6 +107,7 @@ extern "C" void psxhip_adpcm_release_blocks(void) { g_blocks.release(); }
 
 struct psxhip_adpcm_session {
     int device, n_chains, n_chunks;
+    int beam = 0;               // 0: the plain encoder's kernels; 1 .. 4: adpcm_beam_kernels.hip (psxhip_adpcm_session_set_beam)
     bool speculated;
     hipStream_t stream;
     psxhip_adpcm_chunk_job_t job;
@@ -209,6 +239,28 @@ extern "C" int psxhip_adpcm_session_last_timing(const psxhip_adpcm_session_t* s,
     return PSXHIP_OK;
 }
 extern "C" const char* psxhip_adpcm_kernel_rev(void) { return PSXHIP_ADPCM_KERNEL_REV; }
+extern "C" const char* psxhip_adpcm_beam_kernel_rev(void) { return PSXHIP_ADPCM_BEAM_KERNEL_REV; }
+
+// Which unit encoder the session's launches run: 0 the plain one (the default), 1 .. 4 the beam.  The records a session holds come
+// from one encoder: the width is set before the first run or after a reset, not in between.
+extern "C" int psxhip_adpcm_session_set_beam(psxhip_adpcm_session_t* s, int beam) {
+    if (!s || beam < 0 || beam > PSXHIP_ADPCM_BEAM_MAX_WIDTH || s->speculated) {
+        psxhip_set_error("adpcm_session_set_beam: bad argument (beam 0 .. 4, before the first run or after a reset)");
+        return PSXHIP_EINVAL;
+    }
+    s->beam = beam;
+    return PSXHIP_OK;
+}
+
+// one speculate (verify = 0) or verify launch of the session's job with the unit encoder the session was given
+static hipError_t session_launch(psxhip_adpcm_session* s, int verify, hipStream_t st) {
+    if (s->beam == 0) return psxhip_adpcm_chunks_launch(&s->job, verify, st);
+    psxhip_adpcm_beam_chunk_job_t bj;
+    bj.job = s->job;
+    bj.beam = s->beam;
+    bj.unit_err = nullptr;
+    return psxhip_adpcm_beam_chunks_launch(&bj, verify, st);
+}
 
 extern "C" void psxhip_adpcm_session_reset(psxhip_adpcm_session_t* s) {
     if (s) s->speculated = false;        // the next run speculates again from scratch (same block, same chunk tables)
@@ -251,7 +303,7 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
             s->job.changed = s->d_flags;
             s->job.changed_before = nullptr;
             if (timed) HIP_TRY(hipEventRecord(s->ev[0], st), PSXHIP_EDEVICE);
-            HIP_TRY(psxhip_adpcm_chunks_launch(&s->job, 0, st), PSXHIP_EDEVICE);
+            HIP_TRY(session_launch(s, 0, st), PSXHIP_EDEVICE);
             if (timed) HIP_TRY(hipEventRecord(s->ev[1], st), PSXHIP_EDEVICE);
             s->speculated = true;
             if (any_change) *any_change = 1;
@@ -260,7 +312,7 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
             [&](int* flag, const int* flag_before) {
                 s->job.changed = flag;
                 s->job.changed_before = flag_before;
-                return psxhip_adpcm_chunks_launch(&s->job, 1, st);
+                return session_launch(s, 1, st);
             },
             s->d_flags, s->h_flags, st, max_passes, "adpcm_session_run", &changed);
         if (passes < 0) return passes;
@@ -280,10 +332,10 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
     return passes;
 }
 
-extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains,
-                                                  const int32_t* unit_base, int n_chains, int filter_count, int bits,
-                                                  psxhip_adpcm_state_t* d_states, uint8_t* d_units, int chunk_units,
-                                                  int warmup_units, int max_passes, void* stream) {
+// the chunked call with either unit encoder (beam 0: the plain one)
+static int encode_chains_chunked(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains, const int32_t* unit_base,
+                                 int n_chains, int filter_count, int bits, int beam, psxhip_adpcm_state_t* d_states, uint8_t* d_units,
+                                 int chunk_units, int warmup_units, int max_passes, void* stream) {
     if (!d_states) {
         psxhip_set_error("adpcm_encode_chains_chunked: bad argument");
         return PSXHIP_EINVAL;
@@ -293,6 +345,7 @@ extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_s
     int rc = psxhip_adpcm_session_create(&s, device, d_samples, chains, unit_base, nullptr, n_chains, filter_count, bits, d_units,
                                          chunk_units, warmup_units, stream);
     if (rc) return rc;
+    s->beam = beam;
     // d_states travels on the caller's stream, like everything else here: earlier work on that stream may still be writing it (a serial
     // psxhip_adpcm_encode_chains_device, say), and a copy on the null stream does not wait for a non-blocking stream
     std::vector<psxhip_adpcm_state_t> st((size_t)n_chains);
@@ -314,6 +367,26 @@ extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_s
         return PSXHIP_EDEVICE;
     }
     return passes;
+}
+
+extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains,
+                                                  const int32_t* unit_base, int n_chains, int filter_count, int bits,
+                                                  psxhip_adpcm_state_t* d_states, uint8_t* d_units, int chunk_units,
+                                                  int warmup_units, int max_passes, void* stream) {
+    return encode_chains_chunked(device, d_samples, chains, unit_base, n_chains, filter_count, bits, 0, d_states, d_units, chunk_units,
+                                 warmup_units, max_passes, stream);
+}
+
+extern "C" int psxhip_adpcm_beam_encode_chains_chunked(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains,
+                                                       const int32_t* unit_base, int n_chains, int filter_count, int bits,
+                                                       psxhip_adpcm_state_t* d_states, uint8_t* d_units, int beam, int chunk_units,
+                                                       int warmup_units, int max_passes, void* stream) {
+    if (beam < 1 || beam > PSXHIP_ADPCM_BEAM_MAX_WIDTH) {
+        psxhip_set_error("adpcm_beam_encode_chains_chunked: bad argument (beam 1 .. 4)");
+        return PSXHIP_EINVAL;
+    }
+    return encode_chains_chunked(device, d_samples, chains, unit_base, n_chains, filter_count, bits, beam, d_states, d_units, chunk_units,
+                                 warmup_units, max_passes, stream);
 }
 
 extern "C" int psxhip_spu_pack_device(int device, const uint8_t* d_units, int n_blocks, uint8_t* d_out, void* stream) {

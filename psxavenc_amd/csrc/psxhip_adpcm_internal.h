@@ -72,6 +72,24 @@ hipError_t psxhip_adpcm_final_states_launch(const psxhip_adpcm_chain_t *chains, 
                                             const psxhip_adpcm_state_t *unit_states, psxhip_adpcm_state_t *states, void *stream);
 hipError_t psxhip_spu_pack_launch(const uint8_t *units, int n_blocks, uint8_t *out, void *stream);
 
+/* ---- adpcm_beam_kernels.hip: the encoder with a delayed decision inside the unit ("psxhip ADPCM beam v1") ---- */
+/* bumped with every change to adpcm_beam_kernels.hip */
+#define PSXHIP_ADPCM_BEAM_KERNEL_REV "adpcm-beam-k1.0"
+/* adpcm_beam_chains_kernel: every chain serially, four chains per wavefront */
+typedef struct {
+	psxhip_adpcm_chain_job_t job;
+	int beam;                        /* 1 .. 4 */
+	uint32_t *unit_err;              /* optional: the winner's e per record index */
+} psxhip_adpcm_beam_chain_job_t;
+hipError_t psxhip_adpcm_beam_chains_launch(const psxhip_adpcm_beam_chain_job_t *j, void *stream);
+/* adpcm_beam_chunks_kernel: the tables and words of adpcm_chunks_kernel, four chunks per wavefront */
+typedef struct {
+	psxhip_adpcm_chunk_job_t job;
+	int beam;
+	uint32_t *unit_err;              /* optional */
+} psxhip_adpcm_beam_chunk_job_t;
+hipError_t psxhip_adpcm_beam_chunks_launch(const psxhip_adpcm_beam_chunk_job_t *j, int verify, void *stream);
+
 /* ---- adpcm_decode_kernels.hip: the decoder ---- */
 /* adpcm_decode_kernel: serial per chain, or chunks of chains (speculate, verify passes) */
 typedef struct {

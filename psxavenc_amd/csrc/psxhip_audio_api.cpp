@@ -158,9 +158,36 @@ extern "C" void psxhip_release_scratch(void) {
     g_call.release();
 }
 
-extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples, int n_streams, int64_t stream_stride,
-                                              int pitch, int samples_per_stream, psxhip_adpcm_state_t* states,
-                                              uint8_t* out, int64_t out_stride) {
+// the chains of a host-buffer batch with either unit encoder (beam 0: the plain one), serial or cut along time
+static int encode_batch_chains(int device, const int16_t* d_samples, const std::vector<psxhip_adpcm_chain_t>& chains,
+                               const std::vector<int32_t>& base, const psxhip_adpcm_chain_t* d_chains, const int32_t* d_base,
+                               int units_per_chain, int rows, int filter_count, int bits, int beam, psxhip_adpcm_state_t* d_states,
+                               uint8_t* d_units, hipStream_t st) {
+    const int n = (int)chains.size();
+    if (units_per_chain >= psxhip_adpcm_chunked_threshold(n)) {
+        // long streams: parallel along time as well (speculate-and-verify; same bytes as the serial chain kernel)
+        HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
+        int chunk_units, warmup_units;
+        psxhip_adpcm_pick_chunking((long long)units_per_chain * n, rows, device, &chunk_units, &warmup_units);
+        const int rc = beam ? psxhip_adpcm_beam_encode_chains_chunked(device, d_samples, chains.data(), base.data(), n, filter_count, bits,
+                                                                      d_states, d_units, beam, chunk_units, warmup_units, 0, st)
+                            : psxhip_adpcm_encode_chains_chunked(device, d_samples, chains.data(), base.data(), n, filter_count, bits,
+                                                                 d_states, d_units, chunk_units, warmup_units, 0, st);
+        return rc < 0 ? rc : PSXHIP_OK;
+    }
+    return beam ? psxhip_adpcm_beam_encode_chains_device(device, d_samples, d_chains, d_base, n, filter_count, bits, beam, d_states, d_units,
+                                                         nullptr, st)
+                : psxhip_adpcm_encode_chains_device(device, d_samples, d_chains, d_base, n, filter_count, bits, d_states, d_units, st);
+}
+
+static bool bad_beam(int beam, const char* who) {
+    if (beam >= 1 && beam <= PSXHIP_ADPCM_BEAM_MAX_WIDTH) return false;
+    psxhip_set_error("%s: bad argument (beam 1 .. 4)", who);
+    return true;
+}
+
+static int spu_encode_streams(int device, const int16_t* samples, int n_streams, int64_t stream_stride, int pitch, int samples_per_stream,
+                              psxhip_adpcm_state_t* states, uint8_t* out, int64_t out_stride, int beam) {
     if (!samples || !states || !out || n_streams < 0 || samples_per_stream < 0 || pitch < 1) {
         psxhip_set_error("spu_encode_streams_host: bad argument");
         return PSXHIP_EINVAL;
@@ -177,7 +204,7 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
     if (rc) return rc;
 
     // ---- the reference's call pattern (a few streams, a few blocks): one launch, no copies (see CallScratch)
-    if (n_streams <= 4 && n_units < psxhip_adpcm_chunked_threshold(n_streams) && (size_t)n_streams * ((size_t)n_units * 28 + 8) <= (size_t)PSXHIP_ADPCM_CALL_STAGE_MAX &&
+    if (beam == 0 && n_streams <= 4 && n_units < psxhip_adpcm_chunked_threshold(n_streams) && (size_t)n_streams * ((size_t)n_units * 28 + 8) <= (size_t)PSXHIP_ADPCM_CALL_STAGE_MAX &&
         (size_t)n_streams * bytes <= CallScratch::kOut && g_call.ready(device)) {
         psxhip_adpcm_call_job_t a;
         memset(&a, 0, sizeof a);
@@ -231,19 +258,9 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
     HIP_TRY(hipMemcpyAsync(d_c.p, chains.data(), chains.size() * sizeof(chains[0]), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_b.p, base.data(), base.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_st.p, states, n_streams * sizeof(psxhip_adpcm_state_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    if (n_units >= psxhip_adpcm_chunked_threshold(n_streams)) {
-        // long streams: parallel along time as well (speculate-and-verify; same bytes as the serial chain kernel)
-        HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
-        int chunk_units, warmup_units;
-        psxhip_adpcm_pick_chunking((long long)n_units * n_streams, 4, device, &chunk_units, &warmup_units);
-        rc = psxhip_adpcm_encode_chains_chunked(device, d_s.as<int16_t>(), chains.data(), base.data(), n_streams, 5, 4,
-                                                d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), chunk_units, warmup_units, 0, st);
-        if (rc < 0) return rc;
-    } else {
-        rc = psxhip_adpcm_encode_chains_device(device, d_s.as<int16_t>(), d_c.as<psxhip_adpcm_chain_t>(), d_b.as<int32_t>(),
-                                               n_streams, 5, 4, d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), st);
-        if (rc) return rc;
-    }
+    rc = encode_batch_chains(device, d_s.as<int16_t>(), chains, base, d_c.as<psxhip_adpcm_chain_t>(), d_b.as<int32_t>(), n_units, 4, 5, 4, beam,
+                             d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), st);
+    if (rc) return rc;
     rc = psxhip_spu_pack_device(device, d_u.as<uint8_t>(), n_streams * n_units, d_o.as<uint8_t>(), st);
     if (rc) return rc;
     HIP_TRY(hipMemcpy2DAsync(out, (size_t)out_stride, d_o.p, (size_t)bytes, (size_t)bytes, (size_t)n_streams,
@@ -251,6 +268,32 @@ extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples
     HIP_TRY(hipMemcpyAsync(states, d_st.p, n_streams * sizeof(psxhip_adpcm_state_t), hipMemcpyDeviceToHost, st), PSXHIP_EDEVICE);
     HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
     return bytes;
+}
+
+extern "C" int psxhip_spu_encode_streams_host(int device, const int16_t* samples, int n_streams, int64_t stream_stride,
+                                              int pitch, int samples_per_stream, psxhip_adpcm_state_t* states,
+                                              uint8_t* out, int64_t out_stride) {
+    return spu_encode_streams(device, samples, n_streams, stream_stride, pitch, samples_per_stream, states, out, out_stride, 0);
+}
+
+extern "C" int psxhip_spu_encode_streams_host_beam(int device, const int16_t* samples, int n_streams, int64_t stream_stride,
+                                                   int pitch, int samples_per_stream, psxhip_adpcm_state_t* states,
+                                                   uint8_t* out, int64_t out_stride, int beam) {
+    if (bad_beam(beam, "spu_encode_streams_host_beam")) return PSXHIP_EINVAL;
+    return spu_encode_streams(device, samples, n_streams, stream_stride, pitch, samples_per_stream, states, out, out_stride, beam);
+}
+
+static int xa_encode_streams(int device, int format, int stereo, int frequency, int bits, int file_number, int channel_number,
+                             const int16_t* samples, int n_streams, int64_t stream_stride, int samples_per_stream, const int32_t* lbas,
+                             psxhip_adpcm_state_t* states, uint8_t* out, int64_t out_stride, int finalize, const uint8_t* eof_flags, int beam);
+
+extern "C" int psxhip_xa_encode_streams_host_beam(int device, int format, int stereo, int frequency, int bits, int file_number,
+                                                  int channel_number, const int16_t* samples, int n_streams, int64_t stream_stride,
+                                                  int samples_per_stream, const int32_t* lbas, psxhip_adpcm_state_t* states,
+                                                  uint8_t* out, int64_t out_stride, int finalize, int beam) {
+    if (bad_beam(beam, "xa_encode_streams_host_beam")) return PSXHIP_EINVAL;
+    return xa_encode_streams(device, format, stereo, frequency, bits, file_number, channel_number, samples, n_streams, stream_stride,
+                             samples_per_stream, lbas, states, out, out_stride, finalize, nullptr, beam);
 }
 
 extern "C" int psxhip_xa_encode_streams_host(int device, int format, int stereo, int frequency, int bits, int file_number,
@@ -268,6 +311,13 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
                                                    int64_t stream_stride, int samples_per_stream, const int32_t* lbas,
                                                    psxhip_adpcm_state_t* states, uint8_t* out, int64_t out_stride, int finalize,
                                                    const uint8_t* eof_flags) {
+    return xa_encode_streams(device, format, stereo, frequency, bits, file_number, channel_number, samples, n_streams, stream_stride,
+                             samples_per_stream, lbas, states, out, out_stride, finalize, eof_flags, 0);
+}
+
+static int xa_encode_streams(int device, int format, int stereo, int frequency, int bits, int file_number, int channel_number,
+                             const int16_t* samples, int n_streams, int64_t stream_stride, int samples_per_stream, const int32_t* lbas,
+                             psxhip_adpcm_state_t* states, uint8_t* out, int64_t out_stride, int finalize, const uint8_t* eof_flags, int beam) {
     if (!samples || !states || !out || n_streams < 0 || samples_per_stream < 0 || (bits != 4 && bits != 8) ||
         (format != 0 && format != 1)) {
         psxhip_set_error("xa_encode_streams_host: bad argument");
@@ -295,7 +345,7 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
     if (n_streams == 1) stream_stride = (int64_t)per;             // a single stream needs no stride
     // ---- the reference's call pattern (one stream, a sector or two per call, filefmt.c:184,476-491): chains + assembly, two
     //      launches, no copies (see CallScratch)
-    if (n_streams == 1 && sectors <= 6 && ((per + 7) & ~(size_t)7) <= (size_t)PSXHIP_ADPCM_CALL_STAGE_MAX && (size_t)bytes <= CallScratch::kOut &&
+    if (beam == 0 && n_streams == 1 && sectors <= 6 && ((per + 7) & ~(size_t)7) <= (size_t)PSXHIP_ADPCM_CALL_STAGE_MAX && (size_t)bytes <= CallScratch::kOut &&
         g_call.ready(device)) {
         g_pool_device = device;
         DevBuf d_u(4);
@@ -352,18 +402,9 @@ extern "C" int psxhip_xa_encode_streams_host_flags(int device, int format, int s
     HIP_TRY(hipMemcpyAsync(d_b.p, base.data(), base.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_st.p, states, chains.size() * sizeof(psxhip_adpcm_state_t), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     HIP_TRY(hipMemcpyAsync(d_e.p, eof.data(), eof.size(), hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    if (units_per_chain >= psxhip_adpcm_chunked_threshold((int)chains.size())) {
-        HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
-        int chunk_units, warmup_units;
-        psxhip_adpcm_pick_chunking((long long)units_per_chain * (long long)chains.size(), 5, device, &chunk_units, &warmup_units);
-        rc = psxhip_adpcm_encode_chains_chunked(device, d_s.as<int16_t>(), chains.data(), base.data(), (int)chains.size(), 4, bits,
-                                                d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), chunk_units, warmup_units, 0, st);
-        if (rc < 0) return rc;
-    } else {
-        rc = psxhip_adpcm_encode_chains_device(device, d_s.as<int16_t>(), d_c.as<psxhip_adpcm_chain_t>(), d_b.as<int32_t>(),
-                                               (int)chains.size(), 4, bits, d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), st);
-        if (rc) return rc;
-    }
+    rc = encode_batch_chains(device, d_s.as<int16_t>(), chains, base, d_c.as<psxhip_adpcm_chain_t>(), d_b.as<int32_t>(), units_per_chain,
+                             beam ? 4 : 5, 4, bits, beam, d_st.as<psxhip_adpcm_state_t>(), d_u.as<uint8_t>(), st);
+    if (rc) return rc;
     for (int i = 0; i < n_streams; i++) {
         rc = psxhip_xa_assemble_device(device, d_u.as<uint8_t>() + (size_t)i * units_per_stream * xa.record_bytes,
                                        sectors, format, stereo, frequency, bits, file_number, channel_number,
