@@ -590,7 +590,10 @@ struct PixelLane {
 };
 __device__ __forceinline__ PixelLane pixel_lane(int lane, int W, int H) {
     PixelLane p;
-    const int blk = lane >> 3, r8 = lane & 7;
+    // Rows in BUTTERFLY order (mdec-k3.12): the lane with lane & 7 == j fetches pixel row {0, 1, 2, 3, 7, 6, 5, 4}[j] of its block, so
+    // a column of the transpose tile holds (d0, d1, d2, d3, d7, d6, d5, d4) and the column pass's pairs (d7, d6) and (d5, d4) are
+    // dwords of the tile as they stand.  The row pass works on a row's own pixels: which lane holds which row is free.
+    const int blk = lane >> 3, j8 = lane & 7, r8 = j8 < 4 ? j8 : 11 - j8;
     const bool is_chroma = blk < 2;
     if (is_chroma) p.lane_off = (uint32_t)W * (uint32_t)H + (uint32_t)r8 * (uint32_t)W;
     else p.lane_off = ((uint32_t)(((blk - 2) >> 1) * 8 + r8)) * (uint32_t)W + (uint32_t)((blk - 2) & 1) * 8u;
@@ -691,7 +694,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         L.dc_plen[tid] = pro_plen;
         L.dc_prefix[tid] = pro_prefix;
     }
-    int16_t* tileT = L.tiles + (size_t)wid * (kWaveTileBytes / 2);    // [6][kTileStride] row-pass output, transposed
+    int16_t* tileT = L.tiles + (size_t)wid * (kWaveTileBytes / 2);    // [6][kTileStride] row-pass output, transposed: output c of a block at c * 8 + j, j = 0..7 the pixel rows 0, 1, 2, 3, 7, 6, 5, 4 (pixel_lane())
     int16_t* tileZ = tileT + 6 * kTileStride;                          // [6][kZStride] coefficients, column-major within a block
     uint32_t* clist = (uint32_t*)tileT;                                // code list of a macroblock (aliases both tiles)
 
@@ -1209,12 +1212,17 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 uint4 q;
                 asm volatile("ds_read2_b64 %0, %2 offset1:1\n\ts_waitcnt lgkmcnt(0)"
                              : "=v"(q), "+s"(ck) : "v"((uint32_t)(uintptr_t)&tileT[blk * kTileStride + r8 * 8]) : "memory");
-                fdct8_col_acc_k(q.x, q.y, __builtin_amdgcn_alignbit(q.w, q.w, 16), __builtin_amdgcn_alignbit(q.z, q.z, 16), ck, d);
-                // -- column 0 holds the block's DC term in d[0] (as an accumulator: value << 17).  v2: its quantised value
-                //    (mdec.c:447-453) takes its place at scan position 0 and travels with the block's DC slot in the code list.
-                //    v3: the DC codes come from the pre-pass (DPCM chain), position 0 holds 0.  Either way lane 0 is never treated
-                //    as an AC coefficient.
-                if (r8 == 0) d[0] = CODEC == 0 ? (int)((uint32_t)quant_dc(d[0] >> 17) << 17) : 0;
+                // (the tile's rows stand in butterfly order, pixel_lane(): q.z = (d7, d6) and q.w = (d5, d4) need no half-swap)
+                fdct8_col_acc_k(q.x, q.y, q.z, q.w, ck, d);
+                // -- column 0 holds the block's DC term in d[0] (as an accumulator: value << 17).  v2: the RAW term leaves like any
+                //    other output and travels with the block's DC slot in the code list; chunk() quantises it with the
+                //    instructions it runs for every entry (lane 0 of the pass's emit quantiser holds the DC divisor 16).  It is
+                //    exactly the sum of the block's 64 level-shifted samples -- the row pass's output 0 is 16 x the row sum, the
+                //    column pass's (sum + 8) >> 4 -- so it lies in [-8192, 8128]: an int16 tile slot and the entry's 17 bits hold it.
+                //    v3: the DC codes come from the pre-pass (DPCM chain, L.dcv); the raw term sits at position 0 all the same and
+                //    nobody reads it.  Either way lane 0 is never treated as an AC coefficient: the pilot, count_mb() and the
+                //    dense path put 0 there, build_list() keeps lane 0 whatever it holds, the chunks test is_ac.  So the column
+                //    pass has no masked region.
                 // the column's 8 outputs (rows 0..7) leave as one 16-byte store; scan order is applied by the readers (LaneConst::zsrc)
                 uint4 o;
                 o.x = pack_sh17(d[1], d[0]);
@@ -1306,6 +1314,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
         group_sync(1);
         if (L.scalars[S_PILOT_GUESS] == 0) {
         float cfp[kPilotPerWave][6];
+        // (the sample's size as a value made here: compared with the kernel's invariant n_pilot, "has this wavefront a macroblock
+        //  in round i" is hoisted out of the frame loop as a 64-bit lane mask per round, spilled there and fetched back two lane
+        //  reads at a time at every use -- more of them than tests/test_kernel_resources.py allows around the pilot once the
+        //  column pass's masked region is gone (mdec-k3.12); from this copy it is one scalar compare where it is used)
+        int npl = n_pilot;
+        asm volatile("" : "+s"(npl));
         // (Zeroed where the pilot starts: unset, the select below kept the previous frame's six values alive across the whole pass
         //  loop -- two of them spilled to scratch as soon as the loop held the gather's tables in registers.)
         if constexpr (kHoldTables) {
@@ -1315,7 +1329,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
 #pragma unroll
         for (int i = 0; i < kPilotPerWave; i++) {
             const int pi = wid + i * kWavesPerGroup;
-            if (pi < n_pilot) {
+            if (pi < npl) {
                 // The sample: rows spread evenly, columns by the golden ratio (a Kronecker lattice).  Evenly spaced RASTER indices looked
                 // even and were not: at 640x480 (40 x 30 macroblocks, 12 samples) the stride of 100 lands in two columns only, and a
                 // picture with one busy column -- the synthetic frames' wrap-around edge, a real one's vertical bar -- was estimated
@@ -1335,7 +1349,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 wave_sync();
             }
 #pragma unroll
-            for (int b = 0; b < 6; b++) cfp[i][b] = pi < n_pilot ? cf[b] : 0.0f;
+            for (int b = 0; b < 6; b++) cfp[i][b] = pi < npl ? cf[b] : 0.0f;
         }
         if (tid == 0) {
             L.scalars[S_PILOTED] = 1;
@@ -1461,7 +1475,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 fetch_at(cur_o.x & 0x7FFFFFFFu, cur_o.y & 0xFFFFu);
             }
             const QuantK kc = make_quant(lc.quant, count_scale ? count_scale : 1);
-            const QuantK ke = make_quant(lc.quant, emit_scale ? emit_scale : 1);
+            // v2: lane 0 of the emit quantiser -- scan position 0, what a DC slot's entry fetches in chunk() -- holds the DC term's
+            // divisor, 16 at every scale (mdec.c:671).  Nothing else reads lane 0's ke: an AC entry never has scan position 0.
+            const QuantK ke = make_quant(CODEC == 0 && lane == 0 ? 16 : lc.quant, CODEC == 0 && lane == 0 ? 1 : emit_scale ? emit_scale : 1);
             // v2: a macroblock is counted while the ticket drawn last is below this (0: the pass does not count; kStopCount: until the judge sets that bit)
             // (a value of its own in a scalar register: seen through, the compiler tests "does the pass count" and the ticket's bit apart --
             //  five scalar instructions per macroblock where this is one compare)
@@ -1628,7 +1644,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 if (!valid) continue;
                 mb_done++;
 
-                int ci[6];       // this lane's coefficient (scan position = lane) of each block; lane 0 (the DC slot) holds 0
+                int ci[6];       // this lane's coefficient (scan position = lane) of each block; lane 0 (the DC slot) holds the raw DC term (v2: quantised in chunk(); v3: unused)
 #pragma unroll
                 for (int b = 0; b < 6; b++) ci[b] = (int)tileZ[b * kZStride + lc.zsrc];
                 wave_sync();     // the tiles are free again (the code list aliases them)
@@ -1825,11 +1841,14 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         //  the gate word here would cost the counting passes as much and a scalar register the 12-wavefront shape lacks)
                         if (CODEC == 0 && !cs) cnt16 = len | (deficit << 16);
                         if (CODEC == 0) {
-                            // v2 DC slot: the entry carries the quantised DC; 10 bits (mdec.c:451-453), every slot but the
-                            // macroblock's first also carries the previous block's end-of-block code
+                            // v2 DC slot: the entry carries the raw DC term c, and q above is its magnitude divided by 16, rounded half
+                            // away from zero (mdec.c:447-449, 671) -- ek on a DC slot is lane 0's, the divisor 16, and N = 2|c| + 16 < 2^17
+                            // is inside the domain on which quant_mag() is exact.  |c| <= 8192, so the signed value lies in [-512, 508]:
+                            // the reference's clamp to [-512, 510] (mdec.c:260-267) never binds and is not applied.  10 bits
+                            // (mdec.c:451-453), every slot but the macroblock's first also carries the previous block's end-of-block code
                             if (is_dc) {
-                                const uint32_t eob = i != 0 ? 2u << 10 : 0u;       // (a per-lane constant of a one-chunk list: one and-or)
-                                code = (e & 0x3FFu) | eob;
+                                const uint32_t eob = i != 0 ? 2u << 10 : 0u;       // (a per-lane constant of a one-chunk list)
+                                code = ((((uint32_t)q ^ (0u - negbit)) + negbit) & 0x3FFu) | eob;
                                 len = i != 0 ? 12 : 10;
                             }
                         } else {
