@@ -1126,6 +1126,82 @@ int64_t psxhip_spu_file_size(const psxhip_spu_file_settings_t *settings, int64_t
 int64_t psxhip_spu_file_encode_host(int device, const psxhip_spu_file_settings_t *settings, const int16_t *pcm,
                                     int64_t samples_per_channel, uint8_t *out, size_t out_size);
 
+/* ---------------------------------------------------------------- SPU / VAG sound banks ---- */
+
+/* "psxhip SPU bank v1" (DESIGN.md section 23): many mono SPU / VAG files -- the samples of a sound bank, each with its own length,
+ * rate, loop point and name -- encoded by one call into one device buffer, and the way back.  Every entry is one serial ADPCM chain
+ * from a zero state; its blocks are written straight to their place in the bank (a 4-bit unit record is an SPU block), a second
+ * kernel writes everything that is not a data block.  File i lies at offsets[i] and equals, byte for byte, what
+ * psxhip_spu_file_encode_host writes for {format, the entry's audio_frequency, 1 channel, alignment, the entry's audio_loop_point
+ * and enable_loop, no_leading_dummy, the entry's name}; the bytes between the files, and behind the last up to total, are zero. */
+typedef struct {
+	int32_t format;            /* FORMAT_SPU (2) or FORMAT_VAG (3); 4 and 5 are PSXHIP_EINVAL in this revision */
+	int32_t alignment;         /* per file (filefmt.c:280-285); a positive multiple of 16 here */
+	int32_t no_leading_dummy;  /* FLAG_SPU_NO_LEADING_DUMMY */
+	int32_t bank_alignment;    /* every file starts at a multiple of it; a multiple of 16, 16 .. 65536 */
+	int32_t beam;              /* 0 or 1: the reference's bytes; 2 .. 4: "psxhip ADPCM beam v1" */
+} psxhip_spu_bank_settings_t;
+
+typedef struct {
+	int64_t pcm_offset;        /* element offset of the entry's first sample in the PCM buffer (int16, mono); >= 0 */
+	int64_t samples;           /* 0 .. 0x7FFFFFFF - 28 */
+	int32_t audio_frequency;   /* > 0; goes into the .vag header and into the loop-point arithmetic */
+	int32_t audio_loop_point;  /* milliseconds, < 0 = none */
+	int32_t enable_loop;       /* FLAG_SPU_ENABLE_LOOP */
+	char name[16];             /* .vag name field */
+} psxhip_spu_bank_entry_t;
+
+/* The layout alone; runs without a device.  sizes[i] = psxhip_spu_file_size of entry i's one-file settings; offsets[i] ascend in
+ * entry order, each the end of the file before rounded up to bank_alignment (offsets[0] = 0); *total = the last file's end rounded
+ * up likewise.  offsets, sizes ([n]) and total may each be NULL.  PSXHIP_EINVAL, each with its own text and in this order: n outside
+ * 1 .. 65535; NULL settings or entries; a format other than 2 / 3; an alignment that is no positive multiple of 16; a bank_alignment that is no multiple of 16
+ * in 16 .. 65536; a beam outside 0 .. 4; then per entry: samples out of range, audio_frequency <= 0, pcm_offset < 0; at last a bank
+ * of 2^31 or more 16-byte records (record indices are int32). */
+int psxhip_spu_bank_plan(const psxhip_spu_bank_settings_t *settings, const psxhip_spu_bank_entry_t *entries, int n,
+                         int64_t *offsets, int64_t *sizes, int64_t *total);
+
+/* The context owns the plan and its device tables: the chains and unit bases (entry i's chain reads its PCM and writes -- or, for
+ * the decoder, reads -- the records from its first data block on), the zeroed states, the per-entry rows and the tile table the
+ * kernels read, the decoder's tails.  The refusals of psxhip_spu_bank_plan; PSXHIP_EDEVICE without a GPU.  The calls of one context
+ * share its states and tails: one call of a context at a time (order them on one stream, or wait in between). */
+typedef struct psxhip_spu_bank psxhip_spu_bank_t;
+int psxhip_spu_bank_create(psxhip_spu_bank_t **bank, int device, const psxhip_spu_bank_settings_t *settings,
+                           const psxhip_spu_bank_entry_t *entries, int n);
+void psxhip_spu_bank_destroy(psxhip_spu_bank_t *bank);
+int64_t psxhip_spu_bank_total_bytes(const psxhip_spu_bank_t *bank);
+/* offsets, sizes: [n] each, either may be NULL */
+int psxhip_spu_bank_layout(const psxhip_spu_bank_t *bank, int64_t *offsets, int64_t *sizes);
+
+/* d_pcm: int16 device memory holding every entry's samples at its pcm_offset; d_out: total bytes, 16-byte aligned.  Afterwards every
+ * byte of [0, total) is defined as above and nothing outside is touched.  Every call starts every entry from a zero state.  With
+ * beam >= 2 the data blocks are those of psxhip_spu_encode_streams_host_beam from a zero state, under the same framing.
+ * Asynchronous on `stream` ONLY when the serial chains kernel is chosen: when the longest entry has psxhip's chunked threshold of
+ * units or more (512 with up to 8 entries, else 4096) the entries are encoded by psxhip_adpcm_encode_chains_chunked, in place, and
+ * that call synchronises with `stream`; the framing kernel behind it is asynchronous again. */
+int psxhip_spu_bank_encode_device(psxhip_spu_bank_t *bank, const int16_t *d_pcm, uint8_t *d_out, void *stream);
+/* pcm and out in host memory: pcm_elements >= every entry's pcm_offset + samples, out_size >= total.  Returns total or < 0. */
+int64_t psxhip_spu_bank_encode_host(psxhip_spu_bank_t *bank, const int16_t *pcm, int64_t pcm_elements, uint8_t *out, size_t out_size);
+
+/* The inverse of the framing: d_status[i] (int32, [n], zeroed by the call on the stream) gets the bits below for entry i of the bank
+ * at d_bank (16-byte aligned); a bank this library wrote gives zeros.  The data blocks' other bytes are not judged (the decoder's unit
+ * flags do that).  Asynchronous on `stream`. */
+#define PSXHIP_SPU_BANK_STATUS_HEADER 1    /* one of the 48 header bytes is not what the entry implies */
+#define PSXHIP_SPU_BANK_STATUS_DUMMY 2     /* the leading block is not zero */
+#define PSXHIP_SPU_BANK_STATUS_FLAGS 4     /* byte 1 of a data block is not what the rule puts there */
+#define PSXHIP_SPU_BANK_STATUS_TRAP 8      /* the trailing block differs */
+#define PSXHIP_SPU_BANK_STATUS_PADDING 16  /* a non-zero byte in the file's padding or in the gap behind it */
+int psxhip_spu_bank_check_device(psxhip_spu_bank_t *bank, const uint8_t *d_bank, int32_t *d_status, void *stream);
+
+/* Every entry's data blocks back to PCM, written in the entries' own layout (pcm_offset, samples; nothing is stored past samples):
+ * psxhip_adpcm_decode_chains_device from zero states under the context's chain table over the bank in place.  With d_ref_pcm (the
+ * same layout) and d_entry_sums (uint64 [n][2], 8-byte aligned) given, d_entry_sums[i] = {sum (a - b)^2, sum b^2} as
+ * psxhip_adpcm_sse_device defines them with the decode call's tail: over whole blocks, the reference PCM read as zero past samples.
+ * d_ref_pcm and d_entry_sums come together or not at all.  Asynchronous on `stream`. */
+int psxhip_spu_bank_decode_device(psxhip_spu_bank_t *bank, const uint8_t *d_bank, int16_t *d_pcm_out, const int16_t *d_ref_pcm,
+                                  uint64_t *d_entry_sums, void *stream);
+/* revision of spu_bank_kernels.hip */
+const char *psxhip_spu_bank_kernel_rev(void);
+
 /* ---------------------------------------------------------------- colour conversion + scaling front-end ---- */
 
 /* What the reference leaves to FFmpeg's libswscale (psxavenc/decoding.c:287-311: sws_getContext(... AV_PIX_FMT_NV21,

@@ -22,3 +22,5 @@ from . import disc  # noqa: E402,F401  (disc.kernel_rev(): the revision of the d
 from .disc import disc_check, disc_finish, disc_plan  # noqa: E402,F401
 from . import discread  # noqa: E402,F401  (discread.kernel_rev(): the revision of the disc reader's kernels)
 from .discread import DiscReader, disc_read, disc_read_host  # noqa: E402,F401
+from . import spubank  # noqa: E402,F401  (spubank.kernel_rev(): the revision of the sound bank's kernels)
+from .spubank import SpuBank  # noqa: E402,F401

@@ -15,14 +15,13 @@
 #include "../../include/psxav_hip.h"
 #include "../../include/psxav_mdec.h"
 #include "psxhip_internal.h"
+#include "spu_file_layout.h"
 
 namespace {
 
-constexpr int kBlock = PSX_AUDIO_SPU_BLOCK_SIZE;                 // 16
-constexpr int kSamples = PSX_AUDIO_SPU_SAMPLES_PER_BLOCK;        // 28
-constexpr int kVagHeader = 0x30;                                 // filefmt.c:93
-
-void put_be32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
+constexpr int kBlock = kSpuBlockBytes;                            // 16
+constexpr int kSamples = kSpuBlockSamples;                        // 28
+constexpr int kVagHeader = kVagHeaderBytes;                       // filefmt.c:93
 
 bool interleaved(const psxhip_spu_file_settings_t* s) { return s->format == FORMAT_SPUI || s->format == FORMAT_VAGI; }
 
@@ -39,41 +38,7 @@ bool settings_ok(const psxhip_spu_file_settings_t* s) {
     return true;
 }
 
-// write_vag_header, filefmt.c:95-162
-void vag_header(const psxhip_spu_file_settings_t* s, int size_per_channel, uint8_t* h) {
-    memset(h, 0, kVagHeader);
-    h[0] = 'V'; h[1] = 'A'; h[2] = 'G';
-    h[3] = s->format == FORMAT_VAGI ? 'i' : 'p';
-    put_be32(h + 0x04, 0x20);                                     // version
-    if (s->format == FORMAT_VAGI) {                               // interleave, little endian
-        h[0x08] = (uint8_t)s->audio_interleave;
-        h[0x09] = (uint8_t)(s->audio_interleave >> 8);
-        h[0x0A] = (uint8_t)(s->audio_interleave >> 16);
-        h[0x0B] = (uint8_t)(s->audio_interleave >> 24);
-    }
-    put_be32(h + 0x0C, (uint32_t)size_per_channel);
-    put_be32(h + 0x10, (uint32_t)s->audio_frequency);
-    if (s->format == FORMAT_VAGI && s->audio_loop_point >= 0) {   // loop point in bytes (non-standard)
-        int loop_start_block = (s->audio_loop_point * s->audio_frequency) / (kSamples * 1000);
-        if (!s->no_leading_dummy) loop_start_block++;
-        put_be32(h + 0x14, (uint32_t)(loop_start_block * kBlock));
-    }
-    h[0x1E] = (uint8_t)s->audio_channels;
-    strncpy((char*)(h + 0x20), s->name, 16);
-}
-
-// ---- spu / vag -----------------------------------------------------------------------------------------------
-int64_t spu_layout(const psxhip_spu_file_settings_t* s, int64_t n, int64_t* data_blocks, int64_t* block_count) {
-    const int64_t blocks = (n + kSamples - 1) / kSamples;
-    int64_t count = (s->no_leading_dummy ? 0 : 1) + blocks + (s->enable_loop ? 0 : 1);
-    *data_blocks = blocks;
-    *block_count = count;
-    int64_t bytes = count * kBlock;
-    const int64_t overflow = bytes % s->alignment;
-    if (overflow) bytes += s->alignment - overflow;
-    // the reference seeks past the header, writes the data, then seeks back (filefmt.c:218-219,287-292)
-    return (s->format == FORMAT_VAG ? kVagHeader : 0) + bytes;
-}
+// (vag_header and spu_layout: spu_file_layout.h, which the sound bank reads too)
 
 // ---- spui / vagi ---------------------------------------------------------------------------------------------
 struct SpuiPlan {
@@ -141,10 +106,8 @@ extern "C" int64_t psxhip_spu_file_encode_host(int device, const psxhip_spu_file
             const int rc = psxhip_spu_encode_streams_host(device, pcm, 1, 0, 1, (int)n, &st, data + at * kBlock, blocks * kBlock);
             if (rc < 0) return rc;
         }
-        if (s->audio_loop_point >= 0) {                                    // filefmt.c:234-235,251-252
-            const int64_t loop_start_block = at + ((int64_t)s->audio_loop_point * s->audio_frequency) / (kSamples * 1000);
-            if (loop_start_block >= at && loop_start_block < at + blocks) data[loop_start_block * kBlock + 1] |= PSX_AUDIO_SPU_LOOP_START;
-        }
+        const int64_t loop_start_block = spu_loop_start_data_block(s, blocks);                               // filefmt.c:234-235,251-252
+        if (loop_start_block >= 0) data[(at + loop_start_block) * kBlock + 1] |= PSX_AUDIO_SPU_LOOP_START;
         if (s->enable_loop && blocks) data[(at + blocks - 1) * kBlock + 1] |= PSX_AUDIO_SPU_LOOP_REPEAT;     // filefmt.c:253-254
         if (!s->enable_loop) data[(at + blocks) * kBlock + 1] = PSX_AUDIO_SPU_LOOP_TRAP;                      // trailing looping block, :271-278
         if (s->format == FORMAT_VAG) vag_header(s, (int)(block_count * kBlock), out);
