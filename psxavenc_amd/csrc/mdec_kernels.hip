@@ -296,6 +296,12 @@ __device__ __forceinline__ uint32_t pack_sh17(int hi, int lo) {
     return __builtin_bit_cast(uint32_t, (s16x2)(__builtin_bit_cast(s16x2, p) >> (s16x2){1, 1}));
 }
 
+// (hi >> 16, lo >> 16) as packed int16: the two high halves side by side, nothing else.  The frame kernel's coefficient tile holds
+// these: v' = 2 n + b, the coefficient n = acc >> 17 with the accumulator's bit below it (|n| <= 8192, so v' is an int16).
+__device__ __forceinline__ uint32_t pack_sh16(int hi, int lo) {
+    return __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x07060302u);
+}
+
 // ---------------------------------------------------------------------------------------------
 // The ROW pass on the matrix pipe.  It is the same eight exact integer linear forms over the lane's 8 raw pixels -- an
 // 8 x 8 integer matrix times a pixel vector -- so v_mfma_i32_32x32x16_i8 evaluates it exactly in int32: the pixels are one
@@ -412,7 +418,7 @@ struct Lds {
     uint32_t* out;          // [out_words]   frame output staging, dword j = output bytes 4j..4j+3 (pre-swizzle)
     uint32_t* stg;          // [stg_words]   macroblock bitstreams, each from a dword boundary, same bit order as `out`
     uint32_t* rec;          // [nmb]         per macroblock (encode order): staging dword offset | stream bits << 16
-    uint32_t* mb_off;       // [nmb]         bit offset of each macroblock in the frame's stream
+    uint32_t* mb_off;       // [nmb]         bit position of each macroblock's staged stream in the frame image (scan_offsets())
     int* dc_fn;             // [4 * DC chunks]  v3 DC chains: per 64-element chunk (thr, lo, hi) of its composite + the value entering it
     int16_t* dcv;           // [nmb*6]       per block, encode order: v2 the quantised DC; v3 the quantised DC, then (after the
                             //               chain scan) the DPCM delta -- codes are derived where they are needed
@@ -502,6 +508,15 @@ __device__ __forceinline__ QuantK make_quant(int quant, int scale) {
     QuantK k;
     k.inv = 1.0f / (float)(quant * scale);      // IEEE division
     k.bias = __builtin_fmaf(0.25f, k.inv, 0.5f);
+    return k;
+}
+// The same quantiser for operands that come DOUBLED (the frame kernel's tile and code list hold 2 n): inv' = inv / 2 and the bias
+// 0.5 + 0.5 inv' -- fma(|2 n|, inv / 2, bias) is the same real number rounded once, and halving a float is exact, so the result is
+// quant_mag(n, make_quant(quant, scale)) bit for bit (tests/test_mdec_k313_cpu.py checks every divisor and operand).
+__device__ __forceinline__ QuantK make_quant_doubled(int quant, int scale) {
+    QuantK k;
+    k.inv = 0.5f * (1.0f / (float)(quant * scale));
+    k.bias = __builtin_fmaf(0.5f, k.inv, 0.5f);
     return k;
 }
 __device__ __forceinline__ int quant_mag(float cf, const QuantK& k) {
@@ -763,8 +778,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             const int bits = mbe < nmb ? (int)(L.rec[mbe] >> 16) : 0;
             const int incl = wave::inclusive_scan_add(bits);
             const uint32_t D = carry + (uint32_t)(incl - bits);
-            if (mbe < nmb) L.mb_off[mbe] = D;
-            int tile = mbe < nmb ? (int)((2u + (D >> 5)) / (uint32_t)job.out_tile) : 0x7FFF;
+            // (stored as the IMAGE bit the staged stream goes to: behind the 64 header bits, and two bits earlier than its own codes --
+            //  a macroblock's stream starts with the end-of-block code of the block before it, chunk())
+            const uint32_t at = D + 62u;
+            if (mbe < nmb) L.mb_off[mbe] = at;
+            int tile = mbe < nmb ? (int)((at >> 5) / (uint32_t)job.out_tile) : 0x7FFF;
             const int before = __builtin_amdgcn_update_dpp(prev_tile, tile, 0x138, 0xF, 0xF, false);   // wave_shr:1, lane 0 <- carry
             if (mbe < nmb && tile != before && tile <= kMaxTiles) L.scalars[S_TILE_FIRST0 + tile] = mbe;
             prev_tile = __builtin_amdgcn_readlane(tile, 63);
@@ -1225,10 +1243,12 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 //    pass has no masked region.
                 // the column's 8 outputs (rows 0..7) leave as one 16-byte store; scan order is applied by the readers (LaneConst::zsrc)
                 uint4 o;
-                o.x = pack_sh17(d[1], d[0]);
-                o.y = pack_sh17(d[3], d[2]);
-                o.z = pack_sh17(d[5], d[4]);
-                o.w = pack_sh17(d[7], d[6]);
+                // (DOUBLED, with the accumulator's next bit below: acc >> 16 = 2 n + b is the permute alone -- every reader of the tile
+                //  knows, pack_sh16())
+                o.x = pack_sh16(d[1], d[0]);
+                o.y = pack_sh16(d[3], d[2]);
+                o.z = pack_sh16(d[5], d[4]);
+                o.w = pack_sh16(d[7], d[6]);
                 *(uint4*)&tileZ[lane * 8] = o;
             }
             wave_sync();     // tileZ holds the macroblock's coefficients: block b, column c, row r at [b * 64 + c * 8 + r]
@@ -1345,7 +1365,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     dct_mb(ts, b_lo, b_hi);
                 }
 #pragma unroll
-                for (int b = 0; b < 6; b++) cf[b] = lane == 0 ? 0.0f : (float)(int)tileZ[b * kZStride + lc.zsrc];
+                for (int b = 0; b < 6; b++) cf[b] = lane == 0 ? 0.0f : (float)((int)tileZ[b * kZStride + lc.zsrc] >> 1);      // (the tile holds 2 n + b)
                 wave_sync();
             }
 #pragma unroll
@@ -1474,10 +1494,11 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             } else {
                 fetch_at(cur_o.x & 0x7FFFFFFFu, cur_o.y & 0xFFFFu);
             }
-            const QuantK kc = make_quant(lc.quant, count_scale ? count_scale : 1);
+            // (the pass's quantisers work on doubled operands: the tile and the code list hold 2 n)
+            const QuantK kc = make_quant_doubled(lc.quant, count_scale ? count_scale : 1);
             // v2: lane 0 of the emit quantiser -- scan position 0, what a DC slot's entry fetches in chunk() -- holds the DC term's
             // divisor, 16 at every scale (mdec.c:671).  Nothing else reads lane 0's ke: an AC entry never has scan position 0.
-            const QuantK ke = make_quant(CODEC == 0 && lane == 0 ? 16 : lc.quant, CODEC == 0 && lane == 0 ? 1 : emit_scale ? emit_scale : 1);
+            const QuantK ke = make_quant_doubled(CODEC == 0 && lane == 0 ? 16 : lc.quant, CODEC == 0 && lane == 0 ? 1 : emit_scale ? emit_scale : 1);
             // v2: a macroblock is counted while the ticket drawn last is below this (0: the pass does not count; kStopCount: until the judge sets that bit)
             // (a value of its own in a scalar register: seen through, the compiler tests "does the pass count" and the ticket's bit apart --
             //  five scalar instructions per macroblock where this is one compare)
@@ -1489,14 +1510,15 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
             int emit_bits = 0, mb_done = 0;  // wave-uniform
             int prev_len = 0;                // wave-uniform: length of the previous macroblock's list at the count scale (above 128: too long to walk)
             // compaction threshold of this lane: smallest |n| that quantises to non-zero at the list's scale
-            // (|n| >= t  <=>  (unsigned)(n + t - 1) >= 2 t - 1: one add and one compare, no absolute value)
+            // (|n| >= t  <=>  (unsigned)(n + t - 1) >= 2 t - 1: one add and one compare, no absolute value; on the tile's doubled
+            //  values v' = 2 n + b the same test is (unsigned)(v' + 2 t - 2) >= 4 t - 2)
             const uint32_t thr_low = (uint32_t)((lc.quant * (count_scale ? count_scale : 1) + 1) >> 1);
             const uint32_t thr_emit = (uint32_t)((lc.quant * (emit_scale ? emit_scale : 1) + 1) >> 1);
             // (lane 0 -- scan position 0, the block's DC slot -- is always kept: its span is 0, and x + off >= 0 always holds)
             // (the list's scale: the count scale when the pass counts, else the emit scale -- chosen here, once per pass)
             const uint32_t thr_list = count_scale ? thr_low : thr_emit;
-            const uint32_t low_off = thr_list - 1u, low_span = lane == 0 ? 0u : 2u * thr_list - 1u;
-            const uint32_t emit_off = thr_emit - 1u, emit_span = lane == 0 ? 0u : 2u * thr_emit - 1u;
+            const uint32_t low_off = 2u * thr_list - 2u, low_span = lane == 0 ? 0u : 4u * thr_list - 2u;
+            const uint32_t emit_off = 2u * thr_emit - 2u, emit_span = lane == 0 ? 0u : 4u * thr_emit - 2u;
             // per-wavefront totals -> LDS (also used by the checkpoint: flushing resets the partial sums)
             auto flush = [&]() {
                 if (count_scale) {
@@ -1623,7 +1645,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     //  (s_bitcmp1 takes the bit number from a register's low five bits)
                     asm volatile("s_bitcmp1_b32 %0, %1\n\ts_cbranch_scc1 1f\n\ts_setprio 0\n\ts_branch 2f\n1:\ts_setprio 1\n2:" : : "s"(prio_bits4), "s"(it) : "scc");
                 }
+                // (only lane 0's value is read, by readfirstlane below: the other lanes' is left undefined -- an empty statement "makes"
+                //  it -- instead of a zero written by every macroblock)
                 int drawn = 0;
+                asm("" : "=v"(drawn));
                 if (lane == 0) drawn = atomicAdd(&L.scalars[S_MB_NEXT], 1);
                 const bool valid = (int)cur_o.x < 0;
                 const uint32_t rec_byte = cur_o.y >> 16;        // 4 * the macroblock's encode-order index: its record's byte offset
@@ -1644,7 +1669,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                 if (!valid) continue;
                 mb_done++;
 
-                int ci[6];       // this lane's coefficient (scan position = lane) of each block; lane 0 (the DC slot) holds the raw DC term (v2: quantised in chunk(); v3: unused)
+                int ci[6];       // this lane's coefficient (scan position = lane) of each block, as the tile holds it: 2 n + b; lane 0 (the DC slot) holds the raw DC term (v2: quantised in chunk(); v3: unused)
 #pragma unroll
                 for (int b = 0; b < 6; b++) ci[b] = (int)tileZ[b * kZStride + lc.zsrc];
                 wave_sync();     // the tiles are free again (the code list aliases them)
@@ -1653,7 +1678,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     // count-only pass (rare: closing a gap below a scale that is already staged)
                     float cff[6];
 #pragma unroll
-                    for (int b = 0; b < 6; b++) cff[b] = lane == 0 ? 0.0f : (float)ci[b];
+                    for (int b = 0; b < 6; b++) cff[b] = lane == 0 ? 0.0f : (float)(ci[b] & ~1);
                     const int a = count_mb(cff, kc, lc, L.ac_len16);
                     acc_cnt += (a & 0xFF) | ((a >> 8) << 16);
                     continue;
@@ -1669,7 +1694,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     //      everything expensive (VLC look-ups, bit positions, LDS writes) runs on a COMPACTED list, built once
                     //      per macroblock at the pass's LOWER scale (a coefficient that is non-zero at a coarser scale is non-zero
                     //      at every finer one): |n| quantises to non-zero  <=>  2|n| >= d  <=>  |n| >= ceil(d / 2).
-                    //      Entry: [16:0] n (17-bit two's complement), [22:17] scan position.  Lane 0 (scan position 0) is always kept: it
+                    //      Entry: [16:0] 2 n (17-bit two's complement; the tile's bit below n masked off), [22:17] scan position.  Lane 0 (scan position 0) is always kept: it
                     //      marks the block's DC slot, so the list is the macroblock's code sequence DC, AC..., DC, AC...
                     //      A macroblock that is dense at the count scale (a list of more than two chunks) is listed again at the
                     //      emit scale and counted in place (count_mb): walking a long list costs more than it saves.
@@ -1700,7 +1725,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                                      PSX_LIST_BLOCK("c0") PSX_LIST_BLOCK("c1") PSX_LIST_BLOCK("c2")
                                      PSX_LIST_BLOCK("c3") PSX_LIST_BLOCK("c4") PSX_LIST_BLOCK("c5")
                                      : [cb] "+s"(cb), [t] "=&v"(t), [e] "=&v"(e), [tag] "=&v"(tag), [n] "=&s"(n), [sv] "=&s"(sv)
-                                     : [off] "v"(off), [span] "v"(span), [m17] "s"(0x1FFFFu), [lane] "v"(lane),
+                                     : [off] "v"(off), [span] "v"(span), [m17] "s"(0x1FFFEu), [lane] "v"(lane),
                                        [c0] "v"(ci[0]), [c1] "v"(ci[1]), [c2] "v"(ci[2]), [c3] "v"(ci[3]), [c4] "v"(ci[4]), [c5] "v"(ci[5])
                                      : "vcc", "scc", "memory");
 #undef PSX_LIST_BLOCK
@@ -1731,7 +1756,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     if (dense) {
                         float cff[6];
 #pragma unroll
-                        for (int b = 0; b < 6; b++) cff[b] = lane == 0 ? 0.0f : (float)ci[b];
+                        for (int b = 0; b < 6; b++) cff[b] = lane == 0 ? 0.0f : (float)(ci[b] & ~1);
                         const int a = count_mb(cff, kc, lc, L.ac_len16);
                         acc_cnt += (a & 0xFF) | ((a >> 8) << 16);
                         wave_sync();
@@ -1745,8 +1770,9 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     //      Emit scale (coarser): entries whose level drops to 0 fall out; the run is taken from the previous
                     //      SURVIVING entry (ballot, count-leading-zeros below this lane, ds_bpermute).  DC slots always survive,
                     //      so a run never crosses a block.  Each block's 2-bit end-of-block code "10" (mdec.c:501-503) travels
-                    //      as two extra leading bits of the NEXT block's DC code; the macroblock's last one is appended by
-                    //      stage_alloc().
+                    //      as two extra leading bits of the NEXT block's DC code -- the macroblock's last one in front of the next
+                    //      macroblock's first DC code: every DC slot is alike, a macroblock's stream has the bits it always had and
+                    //      lies two bits earlier in the frame (scan_offsets()); the frame's last one is the finisher's.
                     int kcarry_a = 0, kcarry_b = 0, bcarry = 0;
                     // (low / do_count / single are compile-time: as run-time flags they cost a dozen scalar instructions and several
                     //  branches per chunk -- and scalar instructions weigh as much as vector ones here)
@@ -1756,7 +1782,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         const bool live = i < count;
                         uint32_t e = clist[i];                                  // (always inside the wavefront's tiles: i < 384)
                         e = live ? e : (63u << 17);                             // dead lanes: |n| = 0 at scan position 63
-                        const int k = (int)__builtin_amdgcn_ubfe(e, 17, 6);
+                        const int k = (int)(e >> 17);      // (an entry and the dead-lane constant hold nothing above bit 22)
                         const uint32_t negbit = __builtin_amdgcn_ubfe(e, 16, 1);      // the sign as a number: only the escape code needs it as a predicate
                         const bool is_dc = k == 0;
                         const uint64_t dcm = CODEC == 0 ? 0ull : wave::ballot(k == 0);        // (v3: the DC slots' block numbers)
@@ -1767,11 +1793,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(magf) : "v"(e));
                         cnt16 = 0;
                         int kprev;
-                        bool is_last;
                         // the quantiser constants belong to the entry's scan position k, i.e. they sit in lane k's registers
                         QuantK ek;
                         ek.inv = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(k << 2, __builtin_bit_cast(int, ke.inv)));
-                        ek.bias = __builtin_fmaf(0.25f, ek.inv, 0.5f);
+                        ek.bias = __builtin_fmaf(0.5f, ek.inv, 0.5f);
                         // (the survivors' slots, below: the base is wave-uniform and lives in a spilled scalar register.  Fetched HERE, in
                         //  front of the table look-ups: fetched where it is used, behind them, the compiler has put a wait for ALL
                         //  outstanding LDS traffic next to the reload -- one exposed LDS round trip per block, 1.5 % of the kernel)
@@ -1782,7 +1807,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             if (do_count) {
                                 QuantK ck;
                                 ck.inv = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(k << 2, __builtin_bit_cast(int, kc.inv)));
-                                ck.bias = __builtin_fmaf(0.25f, ck.inv, 0.5f);
+                                ck.bias = __builtin_fmaf(0.5f, ck.inv, 0.5f);
                                 const int qa = quant_mag(magf, ck);
                                 // bits | deficit << 16, spread here (carried out of the chunk as the 16-bit table entry it was masked again)
                                 uint32_t lw = L.ac_len16[lut_index(is_ac ? qa : 0, is_ac ? k - ka - 1 : 0)];
@@ -1807,12 +1832,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                                          : "=&s"(sv) : "s"(sm), "v"(kslot), "v"(k) : "memory");          // survivors only
                             typedef const uint32_t __attribute__((address_space(3))) * LdsWord;
                             kprev = (int)*(LdsWord)(uintptr_t)(kslot - 4u);                      // (a wavefront's LDS accesses complete in order)
-                            int last = 63 - __builtin_clzll(sm);              // (DC slots survive: sm != 0)
-                            asm("" : "+s"(last));                             // (the subtraction stays scalar: one vector compare)
-                            is_last = lane == last;
                         } else {
-                            is_last = i == count - 1;
-                            kprev = __builtin_amdgcn_update_dpp(kcarry_b, k, 0x138, 0xF, 0xF, false);
+                            // (a one-chunk list has no carry: lane 0's predecessor is the hardware's zero fill, no register holds the 0)
+                            if (single) kprev = __builtin_amdgcn_update_dpp(0, k, 0x138, 0xF, 0xF, true);
+                            else kprev = __builtin_amdgcn_update_dpp(kcarry_b, k, 0x138, 0xF, 0xF, false);
                             if (!single) kcarry_b = __builtin_amdgcn_readlane(k, 63);
                             ncodes = count - base < 64 ? count - base : 64;      // a list at the emit scale: every entry is a code
                         }
@@ -1845,11 +1868,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             // away from zero (mdec.c:447-449, 671) -- ek on a DC slot is lane 0's, the divisor 16, and N = 2|c| + 16 < 2^17
                             // is inside the domain on which quant_mag() is exact.  |c| <= 8192, so the signed value lies in [-512, 508]:
                             // the reference's clamp to [-512, 510] (mdec.c:260-267) never binds and is not applied.  10 bits
-                            // (mdec.c:451-453), every slot but the macroblock's first also carries the previous block's end-of-block code
+                            // (mdec.c:451-453) behind the previous block's end-of-block code
                             if (is_dc) {
-                                const uint32_t eob = i != 0 ? 2u << 10 : 0u;       // (a per-lane constant of a one-chunk list)
-                                code = ((((uint32_t)q ^ (0u - negbit)) + negbit) & 0x3FFu) | eob;
-                                len = i != 0 ? 12 : 10;
+                                code = ((((uint32_t)q ^ (0u - negbit)) + negbit) & 0x3FFu) | (2u << 10);
+                                len = 12;
                             }
                         } else {
                             // v3 DC slots: block index = number of DC slots before this one in the macroblock's list
@@ -1857,19 +1879,10 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             if (is_dc) {
                                 const int bi = bcarry + wave::popc_below(dcmask);
                                 dc_code<CODEC>((int)L.dcv[mbe * 6 + bi], bi >= 2, L.dc_plen, L.dc_prefix, len, code);
-                                if (bi > 0) {                               // carry the previous block's end-of-block code
-                                    code |= 2u << len;
-                                    len += 2;
-                                }
+                                code |= 2u << len;                          // carry the previous block's end-of-block code
+                                len += 2;
                             }
                             if (!single) bcarry += (int)__builtin_popcountll(dcmask);
-                        }
-                        // the macroblock's LAST code carries the last block's end-of-block code behind it, the way every other
-                        // end-of-block code rides in front of the next block's DC code: no separate two-bit write by one lane
-                        {
-                            const int add = is_last ? 2 : 0;
-                            code = (code << add) | (uint32_t)add;
-                            len += add;
                         }
                     };
                     // staging for a macroblock of `mb_bits` bits (all six end-of-block codes included): returns its bit position
@@ -1877,6 +1890,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     auto stage_alloc = [&](uint32_t mb_bits) -> uint32_t {
                         const int ndw = (int)((mb_bits + 31u) >> 5);
                         int off = 0;
+                        asm("" : "=v"(off));      // (lane 0's value alone is read, as for the ticket draw)
                         if (lane == 0) {
                             // (one masked region: the allocation and the macroblock's record -- position | bits << 16, both below 2^16)
                             off = atomicAdd(&L.scalars[S_STG_NEXT], ndw);
@@ -1906,16 +1920,16 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                             const bool live = i < count;
                             uint32_t e = clist[i];
                             e = live ? e : (63u << 17);
-                            const int k = (int)__builtin_amdgcn_ubfe(e, 17, 6);
+                            const int k = (int)(e >> 17);
                             const bool is_dc = k == 0;
                             const bool is_ac = live && !is_dc;
                             float magf;                                            // (as in chunk(): one SDWA convert)
                             asm("v_cvt_f32_i32_sdwa %0, sext(%1) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0" : "=v"(magf) : "v"(e));
                             QuantK ck, ek;
                             ck.inv = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(k << 2, __builtin_bit_cast(int, kc.inv)));
-                            ck.bias = __builtin_fmaf(0.25f, ck.inv, 0.5f);
+                            ck.bias = __builtin_fmaf(0.5f, ck.inv, 0.5f);
                             ek.inv = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(k << 2, __builtin_bit_cast(int, ke.inv)));
-                            ek.bias = __builtin_fmaf(0.25f, ek.inv, 0.5f);
+                            ek.bias = __builtin_fmaf(0.5f, ek.inv, 0.5f);
                             const int ka = __builtin_amdgcn_update_dpp(kcarry, k, 0x138, 0xF, 0xF, false);   // wave_shr:1, lane 0 <- carry
                             kcarry = __builtin_amdgcn_readlane(k, 63);
                             const int qa = quant_mag(magf, ck);
@@ -2206,7 +2220,7 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                     const int off = (int)(r & 0xFFFFu);
                     int ndw = valid ? (int)(((r >> 16) + 31u) >> 5) : -1;
                     const uint32_t D = valid ? L.mb_off[mbe] : 0u;
-                    const int g0 = 2 + (int)(D >> 5);             // image dword of this macroblock's first staging dword
+                    const int g0 = (int)(D >> 5);                 // image dword of this macroblock's first staging dword
                     const uint32_t sh = D & 31u;
                     if (g0 + ndw < t0 || g0 >= t1) ndw = -1;      // nothing of it in this tile
                     for (int j = j0; wave::ballot(j <= ndw) != 0; j += kMbLanes) {
@@ -2214,18 +2228,21 @@ __global__ __launch_bounds__(WAVES * 64, OCC) void mdec_encode_frames_kernel(con
                         const uint32_t prv = (j >= 1 && j <= ndw) ? L.stg[off + j - 1] : 0u;
                         const uint32_t v = __builtin_amdgcn_alignbit(prv, cur, sh);
                         const int g = g0 + j;
-                        if (v && j <= ndw && g >= t0 && g < t1) atomicOr(&L.out[g - t0], v);
+                        // (g < 2: the two bits in front of the frame's first macroblock -- the end-of-block code of no block -- would
+                        //  land in the header; they are dropped)
+                        if (v && j <= ndw && g >= (t0 < 2 ? 2 : t0) && g < t1) atomicOr(&L.out[g - t0], v);
                     }
                 }
             }
             // ---- end-of-frame code, header, results (mdec.c:710-754): one thread, alongside the merge (the end-of-frame code
             //      shares its dwords with the last macroblock, hence atomic; nothing else lands on the two header dwords)
             if (tid == kThreads - 1) {
-                // end-of-frame code (mdec.c:647-651,710): 10 bits at stream bit total_bits - 10 = image bit 64 + that
-                const uint32_t pos = 64u + (uint32_t)(total_bits - 10);
+                // the LAST block's end-of-block code "10" (every other one rides in front of the next DC code, chunk()) and the
+                // end-of-frame code (mdec.c:647-651,710): 12 bits at stream bit total_bits - 12 = image bit 64 + that
+                const uint32_t pos = 64u + (uint32_t)(total_bits - 12);
                 const int w = (int)(pos >> 5);
                 const uint32_t sb = pos & 31u;
-                const uint64_t tt = (uint64_t)(CODEC == 0 ? 0x1FFu : 0x3FFu) << (64 - sb - 10);
+                const uint64_t tt = (uint64_t)((2u << 10) | (CODEC == 0 ? 0x1FFu : 0x3FFu)) << (64 - sb - 12);
                 const uint32_t hi = (uint32_t)(tt >> 32), lo = (uint32_t)tt;
                 if (w >= t0 && w < t1) atomicOr(&L.out[w - t0], hi);
                 if (lo && w + 1 >= t0 && w + 1 < t1) atomicOr(&L.out[w + 1 - t0], lo);
