@@ -1,8 +1,8 @@
-// psxhip_adpcm_decode.cpp -- the ADPCM decoder's entry points (include/psxav_hip.h).  Device level: argument
-// checks, the chunk tables and the verify passes of the chunked decode, the SSE and disassemble calls.  Host-buffer conveniences
-// (psxhip_spu_decode_streams_host, psxhip_xa_decode_streams_host): their refusals and sizes are reader_plan.h's (StreamsHostShape);
-// they build the chain descriptors, move buffers, call the former.  They launch adpcm_decode_kernels.hip and sector_kernels.hip; no
-// decoding happens on the host.
+// psxhip_adpcm_decode.cpp -- the ADPCM decoder's entry points (include/psxav_hip.h).  What they refuse, the
+// chunk length, the chunk tables and the carving of the workspace, the route and the host-buffer shapes are adpcm_plan.cpp's, without
+// HIP; here the plans are executed.  Device level: the chunked decode with its verify passes, the SSE and disassemble calls.
+// Host-buffer conveniences (psxhip_spu_decode_streams_host, psxhip_xa_decode_streams_host): they build the chain descriptors, move
+// buffers, call the former.  They launch adpcm_decode_kernels.hip and sector_kernels.hip; no decoding happens on the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -10,19 +10,12 @@
 #include <vector>
 
 #include "device_buffer.h"
-#include "host_layout.h"
+#include "adpcm_plan.h"
 #include "psxhip_adpcm_internal.h"
 #include "psxhip_internal.h"
-#include "reader_plan.h"
 #include "verify_passes.h"
 
-namespace {
-
-bool bad_coding(int filter_count, int bits) {
-    return (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || (bits == 8 && filter_count == 5);
-}
-
-}  // namespace
+static_assert(kVerifyBatchMax == kAdpcmVerifyBatchMax, "the workspace holds verify_passes.h's flag words");
 
 // measurement (psxhip_adpcm_decode_set_timing): the calling thread's switch and its last chunked call's two durations
 static thread_local bool g_timing = false;
@@ -45,13 +38,10 @@ extern "C" int psxhip_adpcm_decode_chains_device(int device, const uint8_t* d_un
                                                  const int32_t* d_unit_base, int n_chains, int filter_count, int bits,
                                                  psxhip_adpcm_state_t* d_states, int16_t* d_samples, uint8_t* d_unit_flags, int16_t* d_tail,
                                                  void* stream) {
-    if (n_chains < 0 || bad_coding(filter_count, bits) || (n_chains > 0 && (!d_units || !d_chains || !d_unit_base || !d_states || !d_samples)) ||
-        ((uintptr_t)d_units & 15) || ((uintptr_t)d_samples & 1) || ((uintptr_t)d_tail & 3)) {
-        psxhip_set_error("adpcm_decode_chains: bad argument (bits 4 or 8, filter_count 4 or 5 and 4 with 8 bits, d_units 16-byte aligned, d_tail 4-byte)");
-        return PSXHIP_EINVAL;
-    }
-    const int rc = psxhip_ensure_device(device);
+    int rc = adpcm_decode_chains_check(false, (uintptr_t)d_units, d_chains != nullptr, d_unit_base != nullptr, (uintptr_t)d_states, (uintptr_t)d_samples,
+                                       (uintptr_t)d_tail, n_chains, filter_count, bits);
     if (rc) return rc;
+    if ((rc = psxhip_ensure_device(device))) return rc;
     if (n_chains == 0) return PSXHIP_OK;
     psxhip_adpcm_decode_job_t job;
     memset(&job, 0, sizeof job);
@@ -65,63 +55,22 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
                                                   const int32_t* unit_base, int n_chains, int filter_count, int bits,
                                                   psxhip_adpcm_state_t* d_states, int16_t* d_samples, uint8_t* d_unit_flags, int16_t* d_tail,
                                                   int chunk_units, int warmup_units, int max_passes, void* stream) {
-    if (n_chains < 0 || bad_coding(filter_count, bits) || (n_chains > 0 && (!d_units || !chains || !unit_base || !d_states || !d_samples)) ||
-        ((uintptr_t)d_units & 15) || ((uintptr_t)d_samples & 1) || ((uintptr_t)d_tail & 3)) {
-        psxhip_set_error("adpcm_decode_chains_chunked: bad argument (bits 4 or 8, filter_count 4 or 5 and 4 with 8 bits, d_units 16-byte aligned, d_tail 4-byte)");
-        return PSXHIP_EINVAL;
-    }
-    long long total_units = 0;
-    for (int c = 0; c < n_chains; c++) {
-        if (chains[c].pitch < 1 || chains[c].n_units < 0) {
-            psxhip_set_error("adpcm_decode_chains_chunked: chain %d has pitch %d, n_units %d", c, chains[c].pitch, chains[c].n_units);
-            return PSXHIP_EINVAL;
-        }
-        total_units += chains[c].n_units;
-    }
-    const int rc = psxhip_ensure_device(device);
+    int rc = adpcm_decode_chains_check(true, (uintptr_t)d_units, chains != nullptr, unit_base != nullptr, (uintptr_t)d_states, (uintptr_t)d_samples,
+                                       (uintptr_t)d_tail, n_chains, filter_count, bits);
     if (rc) return rc;
+    long long total_units;
+    if ((rc = adpcm_decode_chunked_chains_check(chains, n_chains, &total_units))) return rc;
+    if ((rc = psxhip_ensure_device(device))) return rc;
     if (total_units == 0) return 0;
     HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
-    if (chunk_units <= 0) {
-        // the encoder's rule (pick_chunking) for wavefronts of 64 chunks: long chunks so that verify needs few passes, enough of them to
-        // fill the device.  A decode wavefront holds 64 chunks and a CU eight such wavefronts: at least four rounds of them
-        int w = 0, n_cu = 0;
-        psxhip_adpcm_pick_chunking(total_units, 64, device, &chunk_units, &w);
-        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || n_cu < 1) n_cu = 256;
-        const long long fill = total_units / (4ll * 8 * 64 * n_cu);
-        const long long want = fill < 256 ? 256 : fill;
-        if (want < chunk_units) chunk_units = (int)want;
-    }
+    if (chunk_units <= 0) chunk_units = adpcm_decode_chunking(total_units, psxhip_adpcm_device_cus(device));
     if (warmup_units < 0) warmup_units = 64;       // decoding is cheap: a long warm-up, not the encoder's
 
-    // the chunk table: chain by chain, the two chains of an interleaved stereo pair chunk by chunk in turns
-    std::vector<int32_t> chunk_chain, chunk_first, chunk_pred, last_chunk((size_t)n_chains, -1);
-    for (int c = 0; c < n_chains;) {
-        const bool pair = c + 1 < n_chains && chains[c].pitch == 2 && chains[c + 1].pitch == 2 && chains[c].n_units > 0 &&
-                          chains[c + 1].sample_offset == chains[c].sample_offset + 1 && chains[c + 1].n_units == chains[c].n_units;
-        const int span = pair ? 2 : 1;
-        for (int f = 0; f < chains[c].n_units; f += chunk_units)
-            for (int k = 0; k < span; k++) {
-                const int32_t idx = (int32_t)chunk_chain.size();
-                last_chunk[c + k] = idx;
-                chunk_chain.push_back(c + k);
-                chunk_first.push_back(f);
-                chunk_pred.push_back(f ? idx - span : -1);
-            }
-        c += span;
-    }
-    const size_t n_chunks = chunk_chain.size();
-    if (n_chunks > 0x7FFFFFFFu) {
-        psxhip_set_error("adpcm_decode_chains_chunked: %zu chunks", n_chunks);
-        return PSXHIP_EINVAL;
-    }
-    BumpOffsets o;
-    const size_t o_chains = o.take(sizeof(psxhip_adpcm_chain_t) * n_chains), o_base = o.take(4 * (size_t)n_chains), o_cc = o.take(4 * n_chunks);
-    const size_t o_cf = o.take(4 * n_chunks), o_cp = o.take(4 * n_chunks), o_last = o.take(4 * (size_t)n_chains);
-    const size_t o_used = o.take(8 * n_chunks), o_end = o.take(8 * n_chunks), o_flags = o.take(sizeof(int) * kVerifyBatchMax);
+    AdpcmDecodePlan p;
+    if ((rc = adpcm_decode_plan(chains, n_chains, chunk_units, &p))) return rc;
+    const size_t n_chunks = p.n_chunks;
     DeviceBuffer ws;
-    const int rc_ws = ws.reserve(o.end);
-    if (rc_ws) return rc_ws;
+    if ((rc = ws.reserve(p.bytes))) return rc;
     uint8_t* const d = ws.as<uint8_t>();
     hipStream_t st = (hipStream_t)stream;
     // declared after the workspace: on every way out the stream has come to rest before the workspace goes, and the timing events go too
@@ -136,22 +85,22 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
     } at_exit{st, false, {nullptr, nullptr, nullptr}};
     hipEvent_t* const ev = at_exit.ev;
     int h_flags[kVerifyBatchMax];
-    HIP_TRY(hipMemcpyAsync(d + o_chains, chains, sizeof(psxhip_adpcm_chain_t) * n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_base, unit_base, 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_cc, chunk_chain.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_cf, chunk_first.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_cp, chunk_pred.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-    HIP_TRY(hipMemcpyAsync(d + o_last, last_chunk.data(), 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + p.o_chains, chains, sizeof(psxhip_adpcm_chain_t) * n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + p.o_base, unit_base, 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + p.o_cc, p.chunk_chain.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + p.o_cf, p.chunk_first.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + p.o_cp, p.chunk_pred.data(), 4 * n_chunks, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+    HIP_TRY(hipMemcpyAsync(d + p.o_last, p.last_chunk.data(), 4 * (size_t)n_chains, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     psxhip_adpcm_decode_job_t job;
     memset(&job, 0, sizeof job);
-    job.units = d_units; job.chains = (const psxhip_adpcm_chain_t*)(d + o_chains); job.unit_base = (const int32_t*)(d + o_base);
+    job.units = d_units; job.chains = (const psxhip_adpcm_chain_t*)(d + p.o_chains); job.unit_base = (const int32_t*)(d + p.o_base);
     job.n_items = (int)n_chunks; job.filter_count = filter_count; job.states = d_states; job.samples = d_samples;
     job.unit_flags = d_unit_flags; job.tail = d_tail;
-    job.chunk_chain = (const int32_t*)(d + o_cc); job.chunk_first = (const int32_t*)(d + o_cf);
-    job.chunk_pred = (const int32_t*)(d + o_cp);
+    job.chunk_chain = (const int32_t*)(d + p.o_cc); job.chunk_first = (const int32_t*)(d + p.o_cf);
+    job.chunk_pred = (const int32_t*)(d + p.o_cp);
     job.chunk_units = chunk_units; job.warmup_units = warmup_units;
-    job.start_used = (unsigned long long*)(d + o_used); job.chunk_end = (unsigned long long*)(d + o_end);
-    int* d_flags = (int*)(d + o_flags);
+    job.start_used = (unsigned long long*)(d + p.o_used); job.chunk_end = (unsigned long long*)(d + p.o_end);
+    int* d_flags = (int*)(d + p.o_flags);
     const bool timed = g_timing;
     if (timed)
         for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreate(&ev[i]), PSXHIP_EDEVICE);
@@ -168,7 +117,7 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
         },
         d_flags, h_flags, st, max_passes, "adpcm_decode_chains_chunked", &changed);
     if (passes < 0) return passes;
-    HIP_TRY(psxhip_adpcm_decode_final_launch((const int32_t*)(d + o_last), (const unsigned long long*)(d + o_end), n_chains, d_states, st),
+    HIP_TRY(psxhip_adpcm_decode_final_launch((const int32_t*)(d + p.o_last), (const unsigned long long*)(d + p.o_end), n_chains, d_states, st),
             PSXHIP_EDEVICE);
     if (timed) {
         HIP_TRY(hipEventRecord(ev[2], st), PSXHIP_EDEVICE);
@@ -184,13 +133,10 @@ extern "C" int psxhip_adpcm_decode_chains_chunked(int device, const uint8_t* d_u
 extern "C" int psxhip_adpcm_sse_device(int device, const int16_t* d_a, const int16_t* d_a_tail, const int16_t* d_b,
                                        const psxhip_adpcm_chain_t* d_chains, int n_chains, uint64_t* d_unit_sse, const int32_t* d_unit_base,
                                        uint64_t* d_chain_sums, void* stream) {
-    if (n_chains < 0 || (n_chains > 0 && (!d_a || !d_b || !d_chains || (d_unit_sse && !d_unit_base))) || ((uintptr_t)d_a & 1) ||
-        ((uintptr_t)d_b & 1) || ((uintptr_t)d_a_tail & 1) || ((uintptr_t)d_unit_sse & 7) || ((uintptr_t)d_chain_sums & 7)) {
-        psxhip_set_error("adpcm_sse: NULL or misaligned argument, negative chain count, or d_unit_sse without d_unit_base");
-        return PSXHIP_EINVAL;
-    }
-    const int rc = psxhip_ensure_device(device);
+    int rc = adpcm_sse_check((uintptr_t)d_a, (uintptr_t)d_a_tail, (uintptr_t)d_b, (uintptr_t)d_chains, n_chains, (uintptr_t)d_unit_sse,
+                             (uintptr_t)d_unit_base, (uintptr_t)d_chain_sums);
     if (rc) return rc;
+    if ((rc = psxhip_ensure_device(device))) return rc;
     if (n_chains == 0) return PSXHIP_OK;
     HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
     if (d_chain_sums) HIP_TRY(hipMemsetAsync(d_chain_sums, 0, (size_t)n_chains * 2 * sizeof(uint64_t), (hipStream_t)stream), PSXHIP_EDEVICE);
@@ -207,13 +153,9 @@ extern "C" int psxhip_adpcm_sse_device(int device, const int16_t* d_a, const int
 
 extern "C" int psxhip_xa_disassemble_device(int device, const uint8_t* d_sectors, int n_sectors, int format, int stereo, int frequency,
                                             int bits, uint8_t* d_units, int32_t* d_sector_status, void* stream) {
-    if (n_sectors < 0 || (format != 0 && format != 1) || (bits != 4 && bits != 8) || (n_sectors > 0 && (!d_sectors || !d_units)) ||
-        ((uintptr_t)d_sectors & 3) || ((uintptr_t)d_units & 3) || ((uintptr_t)d_sector_status & 3)) {
-        psxhip_set_error("xa_disassemble: bad argument (format 0 or 1, bits 4 or 8, pointers 4-byte aligned)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
+    int rc = xa_disassemble_check((uintptr_t)d_sectors, n_sectors, format, bits, (uintptr_t)d_units, (uintptr_t)d_sector_status);
     if (rc) return rc;
+    if ((rc = psxhip_ensure_device(device))) return rc;
     if (n_sectors == 0) return PSXHIP_OK;
     HIP_TRY(hipSetDevice(device), PSXHIP_EDEVICE);
     if ((rc = psxhip_sector_tables(device))) return rc;
@@ -241,7 +183,7 @@ int alloc(DeviceBuffer& b, size_t n) { return b.reserve(n ? n : 4); }
 int decode_chains(int device, const uint8_t* d_units, const std::vector<psxhip_adpcm_chain_t>& chains, const std::vector<int32_t>& base,
                   int filter_count, int bits, psxhip_adpcm_state_t* d_states, int16_t* d_samples, hipStream_t st) {
     const int n = (int)chains.size();
-    if (n > 0 && chains[0].n_units >= psxhip_adpcm_chunked_threshold(n)) {
+    if (n > 0 && adpcm_route_chunked(chains[0].n_units, n)) {
         HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);
         const int rc = psxhip_adpcm_decode_chains_chunked(device, d_units, chains.data(), base.data(), n, filter_count, bits, d_states,
                                                           d_samples, nullptr, nullptr, 0, -1, 0, st);

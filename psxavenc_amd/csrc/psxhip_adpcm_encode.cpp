@@ -1,40 +1,42 @@
-// psxhip_adpcm_encode.cpp -- the device-level entry points of the ADPCM encoder (include/psxav_hip.h): argument checks, the
-// speculate-and-verify session, the SPU pack and XA sector assembly calls.  They fill the kernels' job structs and launch
-// (adpcm_kernels.hip, sector_kernels.hip); no encoding happens on the host.
+// psxhip_adpcm_encode.cpp -- the device-level entry points of the ADPCM encoder (include/psxav_hip.h): the speculate-and-verify
+// session, the SPU pack and XA sector assembly calls.  What they refuse, the session's chunk tables and the carving of its block are
+// adpcm_plan.cpp's, without HIP; here the plans are executed: the kernels' job structs filled and launched (adpcm_kernels.hip,
+// adpcm_beam_kernels.hip, sector_kernels.hip).  No encoding happens on the host.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <vector>
 
-#include "host_layout.h"
+#include "adpcm_plan.h"
 #include "psxhip_adpcm_internal.h"
 #include "psxhip_internal.h"
 #include "verify_passes.h"
 
-// a 4-bit record is stored and read back as one uint4 (store_spu_block, spu_pack_kernel, the sector kernels): 16 bytes, like the decoder's
-// entry points ask for; an 8-bit record goes out in words
-static bool units_misaligned(const void* d_units, int bits) { return ((uintptr_t)d_units & (bits == 4 ? 15 : 3)) != 0; }
+static_assert(kVerifyBatchMax == kAdpcmVerifyBatchMax, "the session's block holds verify_passes.h's flag words");
+
+static void fill_chain_job(psxhip_adpcm_chain_job_t* job, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains, const int32_t* d_unit_base,
+                           int n_chains, int filter_count, int bits, psxhip_adpcm_state_t* d_states, uint8_t* d_units) {
+    job->samples = d_samples;
+    job->chains = d_chains;
+    job->unit_base = d_unit_base;
+    job->n_chains = n_chains;
+    job->filter_count = filter_count;
+    job->range = bits == 4 ? 12 : 8;
+    job->states = d_states;
+    job->units = d_units;
+}
 
 extern "C" int psxhip_adpcm_encode_chains_device(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains,
                                                  const int32_t* d_unit_base, int n_chains, int filter_count, int bits,
                                                  psxhip_adpcm_state_t* d_states, uint8_t* d_units, void* stream) {
-    if (!d_samples || !d_chains || !d_unit_base || !d_states || !d_units || n_chains < 0 ||
-        (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || units_misaligned(d_units, bits)) {
-        psxhip_set_error("adpcm_encode_chains: bad argument (d_units 16-byte aligned for 4-bit records, 4-byte for 8-bit)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
+    int rc = adpcm_encode_chains_check(kEncodeChains, (uintptr_t)d_samples, (uintptr_t)d_chains, (uintptr_t)d_unit_base, (uintptr_t)d_states,
+                                       (uintptr_t)d_units, n_chains, filter_count, bits, 0, 0);
+    if (rc) return rc;
+    rc = psxhip_ensure_device(device);
     if (rc) return rc;
     if (n_chains == 0) return PSXHIP_OK;
     psxhip_adpcm_chain_job_t job;
-    job.samples = d_samples;
-    job.chains = d_chains;
-    job.unit_base = d_unit_base;
-    job.n_chains = n_chains;
-    job.filter_count = filter_count;
-    job.range = bits == 4 ? 12 : 8;
-    job.states = d_states;
-    job.units = d_units;
+    fill_chain_job(&job, d_samples, d_chains, d_unit_base, n_chains, filter_count, bits, d_states, d_units);
     HIP_TRY(psxhip_adpcm_chains_launch(&job, stream), PSXHIP_EDEVICE);
     return PSXHIP_OK;
 }
@@ -44,24 +46,14 @@ extern "C" int psxhip_adpcm_encode_chains_device(int device, const int16_t* d_sa
 extern "C" int psxhip_adpcm_beam_encode_chains_device(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* d_chains,
                                                       const int32_t* d_unit_base, int n_chains, int filter_count, int bits, int beam,
                                                       psxhip_adpcm_state_t* d_states, uint8_t* d_units, uint32_t* d_unit_err, void* stream) {
-    if (!d_samples || !d_chains || !d_unit_base || !d_states || !d_units || n_chains < 0 ||
-        (filter_count != 4 && filter_count != 5) || (bits != 4 && bits != 8) || beam < 1 || beam > PSXHIP_ADPCM_BEAM_MAX_WIDTH ||
-        units_misaligned(d_units, bits) || ((uintptr_t)d_unit_err & 3)) {
-        psxhip_set_error("adpcm_beam_encode_chains: bad argument (beam 1 .. 4; d_units 16-byte aligned for 4-bit records, 4-byte for 8-bit)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
+    int rc = adpcm_encode_chains_check(kBeamEncodeChains, (uintptr_t)d_samples, (uintptr_t)d_chains, (uintptr_t)d_unit_base, (uintptr_t)d_states,
+                                       (uintptr_t)d_units, n_chains, filter_count, bits, beam, (uintptr_t)d_unit_err);
+    if (rc) return rc;
+    rc = psxhip_ensure_device(device);
     if (rc) return rc;
     if (n_chains == 0) return PSXHIP_OK;
     psxhip_adpcm_beam_chain_job_t bj;
-    bj.job.samples = d_samples;
-    bj.job.chains = d_chains;
-    bj.job.unit_base = d_unit_base;
-    bj.job.n_chains = n_chains;
-    bj.job.filter_count = filter_count;
-    bj.job.range = bits == 4 ? 12 : 8;
-    bj.job.states = d_states;
-    bj.job.units = d_units;
+    fill_chain_job(&bj.job, d_samples, d_chains, d_unit_base, n_chains, filter_count, bits, d_states, d_units);
     bj.beam = beam;
     bj.unit_err = d_unit_err;
     HIP_TRY(psxhip_adpcm_beam_chains_launch(&bj, stream), PSXHIP_EDEVICE);
@@ -136,12 +128,10 @@ extern "C" int psxhip_adpcm_session_create(psxhip_adpcm_session_t** out, int dev
                                            uint8_t* d_units, int chunk_units, int warmup_units, void* stream) {
     if (!out) return PSXHIP_EINVAL;
     *out = nullptr;
-    if (!d_samples || !chains || !unit_base || !d_units || n_chains < 0 || (filter_count != 4 && filter_count != 5) ||
-        (bits != 4 && bits != 8) || chunk_units < 1 || warmup_units < 0 || units_misaligned(d_units, bits)) {
-        psxhip_set_error("adpcm_session_create: bad argument (d_units 16-byte aligned for 4-bit records, 4-byte for 8-bit)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
+    int rc = adpcm_session_create_check((uintptr_t)d_samples, chains != nullptr, unit_base != nullptr, (uintptr_t)d_units, n_chains, filter_count, bits,
+                                        chunk_units, warmup_units);
+    if (rc) return rc;
+    rc = psxhip_ensure_device(device);
     if (rc) return rc;
     struct Guard {                       // frees the half-built session on every early return
         psxhip_adpcm_session* p;
@@ -153,69 +143,53 @@ extern "C" int psxhip_adpcm_session_create(psxhip_adpcm_session_t** out, int dev
     s->speculated = false;
     s->stream = (hipStream_t)stream;
 
-    std::vector<int64_t> state_base((size_t)n_chains);
-    std::vector<int32_t> chunk_chain, chunk_first, lead((size_t)n_chains, 0);
-    int64_t total_units = 0;
-    for (int c = 0; c < n_chains; c++) {
-        state_base[(size_t)c] = total_units;
-        for (int f = 0; f < chains[c].n_units; f += chunk_units) {
-            chunk_chain.push_back(c);
-            chunk_first.push_back(f);
-        }
-        total_units += chains[c].n_units;
-        if (lead_units) lead[(size_t)c] = lead_units[c] < 0 ? 0 : lead_units[c];
-    }
-    s->n_chunks = (int)chunk_chain.size();
-    const size_t nc = (size_t)n_chains, nk = (size_t)s->n_chunks;
-    BumpOffsets o;
-    const size_t o_chains = o.take(sizeof(psxhip_adpcm_chain_t) * nc), o_base = o.take(sizeof(int32_t) * nc), o_sbase = o.take(sizeof(int64_t) * nc);
-    const size_t o_lead = o.take(sizeof(int32_t) * nc), o_cstates = o.take(sizeof(psxhip_adpcm_state_t) * nc);
-    const size_t o_final = o.take(sizeof(psxhip_adpcm_state_t) * nc), o_known = o.take(nc), o_flags = o.take(kVerifyBatchMax * sizeof(int));
-    const size_t o_cchain = o.take(sizeof(int32_t) * nk), o_cfirst = o.take(sizeof(int32_t) * nk), o_used = o.take(sizeof(psxhip_adpcm_state_t) * nk);
-    const size_t o_ustates = o.take(sizeof(psxhip_adpcm_state_t) * (size_t)total_units);
-    s->block = (uint8_t*)g_blocks.take(o.end, device, &s->block_cap);
+    AdpcmSessionPlan p;
+    adpcm_session_plan(chains, lead_units, n_chains, chunk_units, &p);
+    s->n_chunks = p.n_chunks;
+    const size_t nc = (size_t)n_chains, nk = (size_t)p.n_chunks;
+    s->block = (uint8_t*)g_blocks.take(p.bytes, device, &s->block_cap);
     if (!s->block) {
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, o.end), PSXHIP_ENOMEM);
-        s->block = (uint8_t*)p;
-        s->block_cap = o.end;
+        void* fresh = nullptr;
+        HIP_TRY(hipMalloc(&fresh, p.bytes), PSXHIP_ENOMEM);
+        s->block = (uint8_t*)fresh;
+        s->block_cap = p.bytes;
     }
     uint8_t* const d = s->block;
     hipStream_t st = s->stream;
     if (n_chains) {
-        HIP_TRY(hipMemcpyAsync(d + o_chains, chains, sizeof(psxhip_adpcm_chain_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-        HIP_TRY(hipMemcpyAsync(d + o_base, unit_base, sizeof(int32_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-        HIP_TRY(hipMemcpyAsync(d + o_sbase, state_base.data(), sizeof(int64_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-        HIP_TRY(hipMemcpyAsync(d + o_lead, lead.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d + p.o_chains, chains, sizeof(psxhip_adpcm_chain_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d + p.o_base, unit_base, sizeof(int32_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d + p.o_sbase, p.state_base.data(), sizeof(int64_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d + p.o_lead, p.lead.data(), sizeof(int32_t) * nc, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     }
     if (s->n_chunks) {
-        HIP_TRY(hipMemcpyAsync(d + o_cchain, chunk_chain.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
-        HIP_TRY(hipMemcpyAsync(d + o_cfirst, chunk_first.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d + p.o_cchain, p.chunk_chain.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
+        HIP_TRY(hipMemcpyAsync(d + p.o_cfirst, p.chunk_first.data(), sizeof(int32_t) * nk, hipMemcpyHostToDevice, st), PSXHIP_EDEVICE);
     }
     HIP_TRY(hipStreamSynchronize(st), PSXHIP_EDEVICE);    // the host vectors go out of scope
 
     psxhip_adpcm_chunk_job_t& job = s->job;
     job.samples = d_samples;
-    job.chains = (const psxhip_adpcm_chain_t*)(d + o_chains);
-    job.unit_base = (const int32_t*)(d + o_base);
-    job.state_base = (const int64_t*)(d + o_sbase);
-    job.chunk_chain = (const int32_t*)(d + o_cchain);
-    job.chunk_first = (const int32_t*)(d + o_cfirst);
+    job.chains = (const psxhip_adpcm_chain_t*)(d + p.o_chains);
+    job.unit_base = (const int32_t*)(d + p.o_base);
+    job.state_base = (const int64_t*)(d + p.o_sbase);
+    job.chunk_chain = (const int32_t*)(d + p.o_cchain);
+    job.chunk_first = (const int32_t*)(d + p.o_cfirst);
     job.n_chunks = s->n_chunks;
     job.chunk_units = chunk_units;
     job.warmup_units = warmup_units;
     job.filter_count = filter_count;
     job.range = bits == 4 ? 12 : 8;
-    job.chain_states = s->d_cstates = (psxhip_adpcm_state_t*)(d + o_cstates);
-    job.lead_units = (const int32_t*)(d + o_lead);
-    job.start_known = s->d_known = d + o_known;
-    job.unit_states = (psxhip_adpcm_state_t*)(d + o_ustates);
-    job.start_used = (psxhip_adpcm_state_t*)(d + o_used);
+    job.chain_states = s->d_cstates = (psxhip_adpcm_state_t*)(d + p.o_cstates);
+    job.lead_units = (const int32_t*)(d + p.o_lead);
+    job.start_known = s->d_known = d + p.o_known;
+    job.unit_states = (psxhip_adpcm_state_t*)(d + p.o_ustates);
+    job.start_used = (psxhip_adpcm_state_t*)(d + p.o_used);
     job.units = d_units;
     job.changed = nullptr;      // set by session_run, per pass
     job.changed_before = nullptr;
-    s->d_final = (psxhip_adpcm_state_t*)(d + o_final);
-    s->d_flags = (int*)(d + o_flags);
+    s->d_final = (psxhip_adpcm_state_t*)(d + p.o_final);
+    s->d_flags = (int*)(d + p.o_flags);
     guard.p = nullptr;                   // ownership passes to the caller
     *out = s;
     return PSXHIP_OK;
@@ -244,10 +218,8 @@ extern "C" const char* psxhip_adpcm_beam_kernel_rev(void) { return PSXHIP_ADPCM_
 // Which unit encoder the session's launches run: 0 the plain one (the default), 1 .. 4 the beam.  The records a session holds come
 // from one encoder: the width is set before the first run or after a reset, not in between.
 extern "C" int psxhip_adpcm_session_set_beam(psxhip_adpcm_session_t* s, int beam) {
-    if (!s || beam < 0 || beam > PSXHIP_ADPCM_BEAM_MAX_WIDTH || s->speculated) {
-        psxhip_set_error("adpcm_session_set_beam: bad argument (beam 0 .. 4, before the first run or after a reset)");
-        return PSXHIP_EINVAL;
-    }
+    const int rc = adpcm_session_beam_check(s != nullptr, beam, s && s->speculated);
+    if (rc) return rc;
     s->beam = beam;
     return PSXHIP_OK;
 }
@@ -332,17 +304,15 @@ extern "C" int psxhip_adpcm_session_run(psxhip_adpcm_session_t* s, const psxhip_
     return passes;
 }
 
-// the chunked call with either unit encoder (beam 0: the plain one)
-static int encode_chains_chunked(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains, const int32_t* unit_base,
+// the chunked call with either unit encoder (the plain entry: beam 0)
+static int encode_chains_chunked(bool beam_entry, int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains, const int32_t* unit_base,
                                  int n_chains, int filter_count, int bits, int beam, psxhip_adpcm_state_t* d_states, uint8_t* d_units,
                                  int chunk_units, int warmup_units, int max_passes, void* stream) {
-    if (!d_states) {
-        psxhip_set_error("adpcm_encode_chains_chunked: bad argument");
-        return PSXHIP_EINVAL;
-    }
+    int rc = adpcm_encode_chunked_check(beam_entry, beam, (uintptr_t)d_states);
+    if (rc) return rc;
     if (n_chains == 0) return 0;
     psxhip_adpcm_session_t* s = nullptr;
-    int rc = psxhip_adpcm_session_create(&s, device, d_samples, chains, unit_base, nullptr, n_chains, filter_count, bits, d_units,
+    rc = psxhip_adpcm_session_create(&s, device, d_samples, chains, unit_base, nullptr, n_chains, filter_count, bits, d_units,
                                          chunk_units, warmup_units, stream);
     if (rc) return rc;
     s->beam = beam;
@@ -373,7 +343,7 @@ extern "C" int psxhip_adpcm_encode_chains_chunked(int device, const int16_t* d_s
                                                   const int32_t* unit_base, int n_chains, int filter_count, int bits,
                                                   psxhip_adpcm_state_t* d_states, uint8_t* d_units, int chunk_units,
                                                   int warmup_units, int max_passes, void* stream) {
-    return encode_chains_chunked(device, d_samples, chains, unit_base, n_chains, filter_count, bits, 0, d_states, d_units, chunk_units,
+    return encode_chains_chunked(false, device, d_samples, chains, unit_base, n_chains, filter_count, bits, 0, d_states, d_units, chunk_units,
                                  warmup_units, max_passes, stream);
 }
 
@@ -381,20 +351,32 @@ extern "C" int psxhip_adpcm_beam_encode_chains_chunked(int device, const int16_t
                                                        const int32_t* unit_base, int n_chains, int filter_count, int bits,
                                                        psxhip_adpcm_state_t* d_states, uint8_t* d_units, int beam, int chunk_units,
                                                        int warmup_units, int max_passes, void* stream) {
-    if (beam < 1 || beam > PSXHIP_ADPCM_BEAM_MAX_WIDTH) {
-        psxhip_set_error("adpcm_beam_encode_chains_chunked: bad argument (beam 1 .. 4)");
-        return PSXHIP_EINVAL;
-    }
-    return encode_chains_chunked(device, d_samples, chains, unit_base, n_chains, filter_count, bits, beam, d_states, d_units, chunk_units,
+    return encode_chains_chunked(true, device, d_samples, chains, unit_base, n_chains, filter_count, bits, beam, d_states, d_units, chunk_units,
                                  warmup_units, max_passes, stream);
 }
 
+// The one place the unit encoder (beam 0: the plain one) and the route meet, for the host-buffer batches and the sound bank: serial
+// under the chain tables on the device, or cut along time under the same tables on the host (that call synchronises).  rows: chunks
+// per wavefront of the encoder that runs (adpcm_chunking)
+int psxhip_adpcm_encode_routed(int device, const int16_t* d_samples, const psxhip_adpcm_chain_t* chains, const int32_t* unit_base,
+                               const psxhip_adpcm_chain_t* d_chains, const int32_t* d_unit_base, int n_chains, bool chunked, long long total_units,
+                               int rows, int filter_count, int bits, int beam, psxhip_adpcm_state_t* d_states, uint8_t* d_units, void* stream) {
+    if (!chunked)
+        return beam ? psxhip_adpcm_beam_encode_chains_device(device, d_samples, d_chains, d_unit_base, n_chains, filter_count, bits, beam, d_states,
+                                                             d_units, nullptr, stream)
+                    : psxhip_adpcm_encode_chains_device(device, d_samples, d_chains, d_unit_base, n_chains, filter_count, bits, d_states, d_units, stream);
+    const AdpcmChunking k = adpcm_chunking(total_units, rows, psxhip_adpcm_device_cus(device));
+    const int rc = beam ? psxhip_adpcm_beam_encode_chains_chunked(device, d_samples, chains, unit_base, n_chains, filter_count, bits, d_states, d_units,
+                                                                  beam, k.chunk_units, k.warmup_units, 0, stream)
+                        : psxhip_adpcm_encode_chains_chunked(device, d_samples, chains, unit_base, n_chains, filter_count, bits, d_states, d_units,
+                                                             k.chunk_units, k.warmup_units, 0, stream);
+    return rc < 0 ? rc : PSXHIP_OK;
+}
+
 extern "C" int psxhip_spu_pack_device(int device, const uint8_t* d_units, int n_blocks, uint8_t* d_out, void* stream) {
-    if (!d_units || !d_out || n_blocks < 0 || ((uintptr_t)d_out & 15) || units_misaligned(d_units, 4)) {
-        psxhip_set_error("spu_pack: bad argument (d_units and d_out must be 16-byte aligned)");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
+    int rc = spu_pack_check((uintptr_t)d_units, n_blocks, (uintptr_t)d_out);
+    if (rc) return rc;
+    rc = psxhip_ensure_device(device);
     if (rc) return rc;
     if (n_blocks == 0) return PSXHIP_OK;
     HIP_TRY(psxhip_spu_pack_launch(d_units, n_blocks, d_out, stream), PSXHIP_EDEVICE);
@@ -414,12 +396,9 @@ extern "C" int psxhip_xa_assemble_scatter(int device, const uint8_t* d_units, in
                                           int frequency, int bits, int file_number, int channel_number, int first_lba,
                                           const uint8_t* d_eof_flags, uint32_t eof_bits, uint8_t* d_out, const int32_t* d_dst_sector,
                                           int n_streams, size_t units_stream_stride, size_t out_stream_stride, void* stream) {
-    if (!d_units || !d_out || n_sectors < 0 || n_streams < 1 || n_streams > 65535 || (format != 0 && format != 1) || (bits != 4 && bits != 8) ||
-        ((uintptr_t)d_out & 3) || (out_stream_stride & 3) || (units_stream_stride & 3)) {
-        psxhip_set_error("xa_assemble: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    int rc = psxhip_ensure_device(device);
+    int rc = xa_assemble_check((uintptr_t)d_units, (uintptr_t)d_out, n_sectors, n_streams, format, bits, units_stream_stride, out_stream_stride);
+    if (rc) return rc;
+    rc = psxhip_ensure_device(device);
     if (rc) return rc;
     if (n_sectors == 0) return PSXHIP_OK;
     rc = psxhip_sector_tables(device);

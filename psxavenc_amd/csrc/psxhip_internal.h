@@ -152,6 +152,12 @@ void psxhip_set_error(const char *fmt, ...);
 #ifdef __cplusplus
 }
 
+/* the device's CU count for adpcm_plan.h's chunking rules; 256 when the query fails (psxhip_audio_api.cpp) */
+int psxhip_adpcm_device_cus(int device);
+/* the ADPCM encoder under chain tables given on the host and on the device alike: serial, or cut along time (psxhip_adpcm_encode.cpp) */
+int psxhip_adpcm_encode_routed(int device, const int16_t *d_samples, const psxhip_adpcm_chain_t *chains, const int32_t *unit_base,
+                               const psxhip_adpcm_chain_t *d_chains, const int32_t *d_unit_base, int n_chains, bool chunked, long long total_units,
+                               int rows, int filter_count, int bits, int beam, psxhip_adpcm_state_t *d_states, uint8_t *d_units, void *stream);
 /* makes `device` current and its tables ready (psxhip_api.cpp); PSXHIP_OK, or the error with its text set */
 int psxhip_ensure_device(int device);
 /* the error every entry point ends with when the machine shows no GPU */

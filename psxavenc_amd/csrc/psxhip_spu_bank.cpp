@@ -8,7 +8,7 @@
 #include <string.h>
 
 #include "device_buffer.h"
-#include "host_layout.h"
+#include "adpcm_plan.h"
 #include "psxhip_internal.h"
 #include "psxhip_spu_bank_internal.h"
 #include "spu_bank_plan.h"
@@ -42,7 +42,7 @@ extern "C" int psxhip_spu_bank_create(psxhip_spu_bank_t** out, int device, const
         ~Guard() { delete p; }
     } guard{new psxhip_spu_bank()};
     psxhip_spu_bank* b = guard.p;
-    int rc = spu_bank_plan_build(settings, entries, n, psxhip_adpcm_chunked_threshold(n), &b->plan);
+    int rc = spu_bank_plan_build(settings, entries, n, adpcm_chunked_threshold(n), &b->plan);
     if (rc) return rc;
     rc = psxhip_ensure_device(device);
     if (rc) return rc;
@@ -112,20 +112,8 @@ extern "C" int psxhip_spu_bank_encode_device(psxhip_spu_bank_t* b, const int16_t
         // every call starts every entry from a zero state; the records go straight into place (a 4-bit record is an SPU block with
         // byte 1 = 0, and unit_base[i] is entry i's first data block)
         HIP_TRY(hipMemsetAsync(b->d_states, 0, sizeof(psxhip_adpcm_state_t) * (size_t)p.n, st), PSXHIP_EDEVICE);
-        const int beam = p.settings.beam;
-        int rc;
-        if (p.chunked) {                // (this call synchronises)
-            int chunk_units, warmup_units;
-            psxhip_adpcm_pick_chunking(p.total_units, 4, b->device, &chunk_units, &warmup_units);
-            rc = beam ? psxhip_adpcm_beam_encode_chains_chunked(b->device, d_pcm, p.chains.data(), p.unit_base.data(), p.n, 5, 4, b->d_states, d_out,
-                                                                beam, chunk_units, warmup_units, 0, st)
-                      : psxhip_adpcm_encode_chains_chunked(b->device, d_pcm, p.chains.data(), p.unit_base.data(), p.n, 5, 4, b->d_states, d_out,
-                                                           chunk_units, warmup_units, 0, st);
-            if (rc > 0) rc = PSXHIP_OK;
-        } else {
-            rc = beam ? psxhip_adpcm_beam_encode_chains_device(b->device, d_pcm, b->d_chains, b->d_base, p.n, 5, 4, beam, b->d_states, d_out, nullptr, st)
-                      : psxhip_adpcm_encode_chains_device(b->device, d_pcm, b->d_chains, b->d_base, p.n, 5, 4, b->d_states, d_out, st);
-        }
+        const int rc = psxhip_adpcm_encode_routed(b->device, d_pcm, p.chains.data(), p.unit_base.data(), b->d_chains, b->d_base, p.n, p.chunked,
+                                                  p.total_units, 4, 5, 4, p.settings.beam, b->d_states, d_out, st);
         if (rc) return rc;
     }
     psxhip_spu_bank_frame_job_t job;

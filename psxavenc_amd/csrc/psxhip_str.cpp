@@ -27,8 +27,8 @@
 #include "../../include/psxav_audio.h"
 #include "../../include/psxav_hip.h"
 #include "../../include/psxav_mdec.h"
+#include "adpcm_plan.h"
 #include "device_buffer.h"
-#include "host_layout.h"
 #include "psxhip_adpcm_internal.h"
 #include "psxhip_internal.h"
 #include "str_plan.h"
@@ -552,7 +552,7 @@ int audio_leg(Dev& d, const DevCall& a) {
     }
     HIP_TRY(hipEventRecord(d.ev_in, a.S), PSXHIP_EDEVICE);
     HIP_TRY(hipStreamWaitEvent(d.astream, d.ev_in, 0), PSXHIP_EDEVICE);
-    const bool chunked = d.units_per_chain >= psxhip_adpcm_chunked_threshold(n_chains);      // (the rule of the host entry points)
+    const bool chunked = adpcm_route_chunked(d.units_per_chain, n_chains);      // (the rule of the host entry points)
     // an error from here on leaves nothing of this call in flight on the caller's buffers
     auto fail = [&](int code) { (void)hipStreamSynchronize(d.astream); (void)hipStreamSynchronize(a.S); return code; };
     if (d.d_pcm != a.d_pcm || d.pcm_stream_stride != a.pcm_stream_stride || d.chunked != chunked) {

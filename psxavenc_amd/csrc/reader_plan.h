@@ -1,6 +1,5 @@
-// reader_plan.h -- what the readers' host layer (psxhip_str_demux.cpp, and the host-buffer conveniences of psxhip_adpcm_decode.cpp)
-// derives from a call's arguments alone: what it refuses, with which text and in which order, how a workspace or a staging buffer is
-// carved, how much audio a PCM buffer holds and what a call returns.  Arithmetic and refusals only (no HIP), like str_plan.h:
+// reader_plan.h -- what the readers' host layer (psxhip_str_demux.cpp) derives from a call's arguments alone: what it refuses, with
+// which text and in which order, how a workspace or a staging buffer is carved, how much audio a PCM buffer holds and what a call returns.  Arithmetic and refusals only (no HIP), like str_plan.h:
 // reader_plan.cpp builds with a host compiler alone and links against nothing but psxhip_set_error and str_plan.cpp
 // (tests/test_reader_plan_cpu.py does so, under the host sanitizers); the launch code only executes these plans.  A plan function
 // returns PSXHIP_OK, or PSXHIP_EINVAL with the error text set.  Pointers come as numbers: nothing here reads through one.  Nothing here
@@ -10,6 +9,7 @@
 #include <stdint.h>
 
 #include "../../include/psxav_hip.h"
+#include "adpcm_plan.h"           // StreamsHostShape, the ADPCM decoder's host conveniences: it lived here, and who includes this header still finds it
 #include "host_layout.h"
 #include "str_plan.h"
 #include "strspu_chunk.h"
@@ -111,71 +111,5 @@ static inline int strspu_read_units(const ReadHostPlan& p, size_t nK) {
 }
 // the STRSPU reader's chains: channel c decodes n_units records from record d * ch + c on, every ch-th
 void strspu_read_chains(psxhip_adpcm_chain_t* chains, int32_t* unit_base, int ch, int d, int n_units);
-
-// ---------------------------------------------------------------------------------------------- psxhip_spu_decode_streams_host, psxhip_xa_decode_streams_host
-// (inline: psxhip_adpcm_decode.cpp's lane program holds that file's text and nothing of reader_plan.cpp)
-struct StreamsHostShape {
-    int channels, units_per_stream;
-    int per_channel;                    // samples a channel of a stream decodes to: what the call returns
-    size_t per, in_bytes;               // a stream's samples (all channels) and source bytes
-    int64_t in_stride, out_stride;      // the caller's, or a stream's own size when there is one stream
-    size_t n_chains, total_sectors;
-    size_t src_bytes, unit_bytes, state_bytes, sample_bytes, status_bytes;
-};
-
-static inline int streams_host_strides(const char* who, int n_streams, int64_t in_stride, int64_t out_stride, StreamsHostShape* p) {
-    if (n_streams == 1) { in_stride = (int64_t)p->in_bytes; out_stride = (int64_t)p->per; }       // one stream: the strides are not looked at
-    if (n_streams > 0 && (in_stride < (int64_t)p->in_bytes || out_stride < (int64_t)p->per)) {
-        psxhip_set_error("%s: in_stride %lld < %zu bytes or out_stride %lld < %zu samples per stream", who, (long long)in_stride, p->in_bytes,
-                         (long long)out_stride, p->per);
-        return PSXHIP_EINVAL;
-    }
-    p->in_stride = in_stride;
-    p->out_stride = out_stride;
-    const size_t S = n_streams > 0 ? (size_t)n_streams : 0;
-    p->n_chains = S * (size_t)p->channels;
-    p->src_bytes = p->in_bytes * S;
-    p->state_bytes = sizeof(psxhip_adpcm_state_t) * p->n_chains;
-    p->sample_bytes = sizeof(int16_t) * p->per * S;
-    return PSXHIP_OK;
-}
-
-static inline int spu_streams_host_shape(int n_streams, int64_t in_stride, int n_blocks, bool buffers, int64_t out_stride, StreamsHostShape* p) {
-    if (n_streams < 0 || n_blocks < 0 || (n_streams > 0 && n_blocks > 0 && !buffers) || (int64_t)n_blocks * 28 > 0x7FFFFFFF) {
-        psxhip_set_error("spu_decode_streams_host: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    *p = StreamsHostShape();
-    p->channels = 1;
-    p->units_per_stream = n_blocks;
-    p->per_channel = n_blocks * 28;
-    p->per = (size_t)p->per_channel;
-    p->in_bytes = (size_t)n_blocks * 16;
-    const int rc = streams_host_strides("spu_decode_streams_host", n_streams, in_stride, out_stride, p);
-    p->unit_bytes = p->src_bytes;       // the source is the unit records
-    return rc;
-}
-
-static inline int xa_streams_host_shape(int format, int stereo, int bits, int n_streams, int64_t in_stride, int n_sectors, bool buffers,
-                                        int64_t out_stride, StreamsHostShape* p) {
-    if (n_streams < 0 || n_sectors < 0 || (bits != 4 && bits != 8) || (format != 0 && format != 1) ||
-        (n_streams > 0 && n_sectors > 0 && !buffers) || (int64_t)n_sectors * 4032 > 0x7FFFFFFF ||
-        (int64_t)n_streams * n_sectors > 0x7FFFFFFF / 144) {
-        psxhip_set_error("xa_decode_streams_host: bad argument");
-        return PSXHIP_EINVAL;
-    }
-    const XaLayout xa = xa_layout(format, stereo, bits);
-    *p = StreamsHostShape();
-    p->channels = xa.channels;
-    p->units_per_stream = n_sectors * xa.units_per_sector;
-    p->per_channel = p->units_per_stream / xa.channels * 28;
-    p->per = (size_t)p->per_channel * xa.channels;
-    p->in_bytes = (size_t)n_sectors * xa.sector_bytes;
-    const int rc = streams_host_strides("xa_decode_streams_host", n_streams, in_stride, out_stride, p);
-    p->total_sectors = (size_t)(n_streams > 0 ? n_streams : 0) * n_sectors;
-    p->unit_bytes = (size_t)(n_streams > 0 ? n_streams : 0) * p->units_per_stream * xa.record_bytes;
-    p->status_bytes = sizeof(int32_t) * p->total_sectors;
-    return rc;
-}
 
 #pragma GCC visibility pop

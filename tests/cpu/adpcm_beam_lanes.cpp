@@ -26,9 +26,11 @@
 #include "hip_lanes/psxhip_api_standin.h"
 
 #include "../../psxavenc_amd/csrc/adpcm_beam_kernels.hip"
+#include "../../psxavenc_amd/csrc/adpcm_plan.cpp"
 #include "../../psxavenc_amd/csrc/psxhip_adpcm_encode.cpp"
 
-// what psxhip_adpcm_encode.cpp takes from adpcm_kernels.hip and sector_kernels.hip
+// what psxhip_adpcm_encode.cpp takes from adpcm_kernels.hip, sector_kernels.hip and the device (its plans are adpcm_plan.cpp's own text)
+int psxhip_adpcm_device_cus(int) { return 4; }
 extern "C" hipError_t psxhip_adpcm_chains_launch(const psxhip_adpcm_chain_job_t*, void*) { return 1; }
 extern "C" hipError_t psxhip_adpcm_chunks_launch(const psxhip_adpcm_chunk_job_t*, int, void*) { return 1; }
 extern "C" hipError_t psxhip_spu_pack_launch(const uint8_t*, int, uint8_t*, void*) { return 1; }

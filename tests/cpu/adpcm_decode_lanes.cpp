@@ -1,5 +1,5 @@
 // tests/cpu/adpcm_decode_lanes.cpp -- TEST INFRASTRUCTURE: runs the text of psxavenc_amd/csrc/adpcm_decode_kernels.hip and of its
-// host layer psxavenc_amd/csrc/psxhip_adpcm_decode.cpp on the CPU under -fsanitize=address,undefined
+// host layer psxavenc_amd/csrc/psxhip_adpcm_decode.cpp (with its plans, adpcm_plan.cpp) on the CPU under -fsanitize=address,undefined
 // (tests/test_adpcm_decode_lanes_cpu.py), behind the wavefront model of the stand-in tests/cpu/hip_lanes.  A record is one call of
 // psxhip_adpcm_decode_chains_device (kind 0), psxhip_adpcm_decode_chains_chunked (kind 1: the host layer's chunk tables, workspace
 // and verify passes) or psxhip_adpcm_sse_device (kind 2).  The host-buffer conveniences of that file decode through the same two
@@ -27,11 +27,11 @@
 #include "hip_lanes/psxhip_api_standin.h"
 
 #include "../../psxavenc_amd/csrc/adpcm_decode_kernels.hip"
+#include "../../psxavenc_amd/csrc/adpcm_plan.cpp"
 #include "../../psxavenc_amd/csrc/psxhip_adpcm_decode.cpp"
 
-// stand-ins for what psxhip_adpcm_decode.cpp takes from the encoder side; the chunking rule is asked only with chunk_units <= 0
-extern "C" void psxhip_adpcm_pick_chunking(long long, int, int, int* chunk_units, int* warmup_units) { *chunk_units = 256; *warmup_units = 8; }
-extern "C" int psxhip_adpcm_chunked_threshold(int) { return 0x7FFFFFFF; }
+// stand-ins for the device-facing wrappers psxhip_adpcm_decode.cpp takes from the encoder side (its plans are adpcm_plan.cpp's own text)
+int psxhip_adpcm_device_cus(int) { return 4; }
 extern "C" int psxhip_sector_tables(int) { return PSXHIP_EDEVICE; }
 extern "C" hipError_t psxhip_xa_disassemble_launch(const psxhip_xa_dis_job_t*, void*) { return hipErrorInvalidValue; }
 

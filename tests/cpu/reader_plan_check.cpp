@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "../../psxavenc_amd/csrc/adpcm_plan.h"          // (the spustreams and xastreams kinds: StreamsHostShape, inline)
 #include "../../psxavenc_amd/csrc/reader_plan.h"
 
 // the error sink: the one symbol the plan modules link against
