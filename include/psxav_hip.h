@@ -1202,6 +1202,47 @@ int psxhip_spu_bank_decode_device(psxhip_spu_bank_t *bank, const uint8_t *d_bank
 /* revision of spu_bank_kernels.hip */
 const char *psxhip_spu_bank_kernel_rev(void);
 
+/* "psxhip SPU loop seam v1" (DESIGN.md section 24).  A looped sample plays intro, body, body, ...: on every repeat the SPU enters the
+ * loop-start block with the decoder state the END of the body left, while the encoder planned that block from the state the intro
+ * left.  An entry's seam block S is the data block that carries LOOP_START when enable_loop is set and the entry has data blocks; 0
+ * when enable_loop is set, no data block carries LOOP_START and no_leading_dummy is set (key-on sets the repeat address to the start
+ * address); none (-1) otherwise.  The body is the data blocks S .. D-1, the intro 0 .. S-1.
+ *
+ * PSXHIP_SPU_SEAM_STEADY: the intro is encoded as always, its end state is s_0 ((0, 0) when S = 0); pass k = 0 .. P-1
+ * (P = PSXHIP_SPU_SEAM_PASSES) encodes the body from s_k with the bank's encoder (plain or beam) and ends in e_k; e_k == s_k keeps
+ * pass k's blocks (the entry is "fixed at pass k": a repeat enters the body in the state the encoder assumed), else s_{k+1} = e_k;
+ * without a fixed point below P, pass 0's blocks -- the blocks of mode OFF -- are kept and the entry reports P.  Entries without a
+ * seam block and everything that is not a data block are byte for byte those of mode OFF.  All launches go to the caller's stream,
+ * nothing is read back, the host never waits.  In this revision a bank in mode STEADY always takes the serial chain kernels, however
+ * long its entries: the chunked route builds host tables and synchronises. */
+#define PSXHIP_SPU_SEAM_OFF 0       /* the default: exactly the launches of psxhip_spu_bank_encode_device as described above */
+#define PSXHIP_SPU_SEAM_STEADY 1
+#define PSXHIP_SPU_SEAM_PASSES 8
+/* Sets the mode of the encodes that follow (and uploads the seam tables the first time STEADY is asked for: the call waits for the
+ * device).  Another mode is PSXHIP_EINVAL.  One call of a context at a time, as above. */
+int psxhip_spu_bank_set_seam(psxhip_spu_bank_t *bank, int mode);
+/* The last encode's outcome per entry into d_pass (int32 [n], 4-byte aligned): -1 = no seam block, k = fixed at pass k, P = no fixed
+ * point (pass 0 kept).  PSXHIP_EINVAL while the mode is OFF.  Asynchronous on `stream`. */
+int psxhip_spu_bank_seam_passes_device(psxhip_spu_bank_t *bank, int32_t *d_pass, void *stream);
+
+/* The seam report, defined on a bank's bytes alone (whoever wrote them).  Pass 1 decodes the data blocks 0 .. D-1 from (0, 0), whole
+ * units as the SPU decodes them: y1, end state b.  Pass 2 decodes S .. D-1 from b: y2, end state b2. */
+typedef struct {
+	int32_t seam_block;     /* S, or -1: no seam block, and every other field is 0 */
+	int32_t first_units;    /* the smallest k with both passes in the same state in front of unit S + k (from there they are identical); D - S if never */
+	int32_t first_peak;     /* max |y2 - y1| */
+	int32_t settled;        /* 1: b2 == b, every later repeat equals pass 2 */
+	uint64_t first_sse;     /* sum (y2 - y1)^2 */
+	uint64_t pass1_err;     /* sum (y1 - x)^2 over the body's whole units, the PCM x read as zero past `samples`; 0 without d_ref_pcm */
+	uint64_t pass2_err;     /* sum (y2 - x)^2 likewise */
+} psxhip_spu_seam_t;
+/* d_bank: the bank, 16-byte aligned; d_ref_pcm: the entries' PCM in their own layout, or NULL; d_seam: [n], 8-byte aligned.  Works
+ * in either mode.  Asynchronous on `stream`. */
+int psxhip_spu_bank_seam_device(psxhip_spu_bank_t *bank, const uint8_t *d_bank, const int16_t *d_ref_pcm, psxhip_spu_seam_t *d_seam,
+                                void *stream);
+/* revision of spu_seam_kernels.hip */
+const char *psxhip_spu_seam_kernel_rev(void);
+
 /* ---------------------------------------------------------------- colour conversion + scaling front-end ---- */
 
 /* What the reference leaves to FFmpeg's libswscale (psxavenc/decoding.c:287-311: sws_getContext(... AV_PIX_FMT_NV21,

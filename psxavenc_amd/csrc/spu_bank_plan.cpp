@@ -23,6 +23,23 @@ psxhip_spu_file_settings_t spu_bank_file_settings(const psxhip_spu_bank_settings
     return f;
 }
 
+int64_t spu_bank_seam_block(const psxhip_spu_file_settings_t* f, int64_t data_blocks) {
+    if (!f->enable_loop || data_blocks <= 0) return -1;
+    const int64_t start = spu_loop_start_data_block(f, data_blocks);
+    if (start >= 0) return start;
+    return f->no_leading_dummy ? 0 : -1;        // key-on sets the repeat address to the start address: block 0, or the dummy block
+}
+
+// units [first, first + count) of entry chain c as a chain of their own
+static psxhip_adpcm_chain_t chain_part(const psxhip_adpcm_chain_t& c, int64_t first, int64_t count) {
+    psxhip_adpcm_chain_t part = c;
+    part.sample_offset = c.sample_offset + first * kSpuBlockSamples;
+    const int64_t limit = (int64_t)c.sample_limit - first * kSpuBlockSamples;
+    part.sample_limit = (int32_t)(limit > 0 ? limit : 0);
+    part.n_units = (int32_t)count;
+    return part;
+}
+
 static int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 int spu_bank_plan_build(const psxhip_spu_bank_settings_t* s, const psxhip_spu_bank_entry_t* entries, int n, int chunked_threshold,
@@ -131,6 +148,32 @@ int spu_bank_plan_build(const psxhip_spu_bank_settings_t* s, const psxhip_spu_ba
             p->tiles.push_back(psxhip_spu_bank_tile_t{i, 1, (int32_t)b, (int32_t)(blocks - b < kSpuBankTile ? blocks - b : kSpuBankTile)});
     }
     p->chunked = p->max_units >= chunked_threshold;
+
+    // the seam tables
+    p->seam_block.resize((size_t)n);
+    p->seam_rows.resize((size_t)n);
+    std::vector<int32_t> intro_slot((size_t)n, -1);
+    for (int i = 0; i < n; i++) {
+        const psxhip_spu_file_settings_t f = spu_bank_file_settings(s, &entries[i]);
+        const int64_t S = spu_bank_seam_block(&f, data_blocks[(size_t)i]);
+        p->seam_block[(size_t)i] = (int32_t)S;
+        p->seam_rows[(size_t)i] = psxhip_spu_seam_row_t{entries[i].pcm_offset, (int32_t)entries[i].samples, p->unit_base[(size_t)i],
+                                                        (int32_t)data_blocks[(size_t)i], (int32_t)S};
+        if (S == 0) continue;
+        intro_slot[(size_t)i] = (int32_t)p->seam_chains.size();
+        p->seam_chains.push_back(S < 0 ? p->chains[(size_t)i] : chain_part(p->chains[(size_t)i], 0, S));
+        p->seam_unit_base.push_back(p->unit_base[(size_t)i]);
+    }
+    p->seam_first = (int)p->seam_chains.size();
+    for (int i = 0; i < n; i++) {
+        const int64_t S = p->seam_block[(size_t)i];
+        if (S < 0) continue;
+        p->seam_chains.push_back(chain_part(p->chains[(size_t)i], S, data_blocks[(size_t)i] - S));
+        p->seam_unit_base.push_back((int32_t)(p->unit_base[(size_t)i] + S));
+        p->seam_body_entry.push_back(i);
+        p->seam_body_intro.push_back(S > 0 ? intro_slot[(size_t)i] : -1);
+    }
+    p->seam_body = (int)p->seam_chains.size() - p->seam_first;
     return PSXHIP_OK;
 }
 

@@ -18,6 +18,8 @@ except Exception:  # pragma: no cover
     torch = None
 
 STATUS_HEADER, STATUS_DUMMY, STATUS_FLAGS, STATUS_TRAP, STATUS_PADDING = 1, 2, 4, 8, 16
+# "psxhip SPU loop seam v1" 
+SEAM_OFF, SEAM_STEADY, SEAM_PASSES = 0, 1, 8
 
 
 class SpuBankSettings(C.Structure):
@@ -30,6 +32,17 @@ class SpuBankEntry(C.Structure):
     """psxhip_spu_bank_entry_t"""
     _fields_ = [("pcm_offset", C.c_int64), ("samples", C.c_int64), ("audio_frequency", C.c_int32), ("audio_loop_point", C.c_int32),
                 ("enable_loop", C.c_int32), ("name", C.c_char * 16)]
+
+
+class SpuSeam(C.Structure):
+    """psxhip_spu_seam_t"""
+    _fields_ = [("seam_block", C.c_int32), ("first_units", C.c_int32), ("first_peak", C.c_int32), ("settled", C.c_int32),
+                ("first_sse", C.c_uint64), ("pass1_err", C.c_uint64), ("pass2_err", C.c_uint64)]
+
+
+# the same record as a numpy dtype: what SpuBank.seam_report returns
+SEAM_DTYPE = np.dtype([("seam_block", "<i4"), ("first_units", "<i4"), ("first_peak", "<i4"), ("settled", "<i4"), ("first_sse", "<u8"),
+                       ("pass1_err", "<u8"), ("pass2_err", "<u8")])
 
 
 def settings(fmt, alignment=64, no_dummy=False, bank_alignment=16, beam=0):
@@ -58,12 +71,20 @@ def _bind():
     L.psxhip_spu_bank_check_device.argtypes = [vp, vp, vp, vp]
     L.psxhip_spu_bank_decode_device.argtypes = [vp, vp, vp, vp, vp, vp]
     L.psxhip_spu_bank_kernel_rev.restype = C.c_char_p
+    L.psxhip_spu_bank_set_seam.argtypes = [vp, i32]
+    L.psxhip_spu_bank_seam_passes_device.argtypes = [vp, vp, vp]
+    L.psxhip_spu_bank_seam_device.argtypes = [vp, vp, vp, vp, vp]
+    L.psxhip_spu_seam_kernel_rev.restype = C.c_char_p
     L._psxhip_spu_bank_bound = True
     return L
 
 
 def kernel_rev():
     return _bind().psxhip_spu_bank_kernel_rev().decode()
+
+
+def seam_kernel_rev():
+    return _bind().psxhip_spu_seam_kernel_rev().decode()
 
 
 def _entry_array(entries):
@@ -157,6 +178,33 @@ class SpuBank:
                                                          d_sums.data_ptr() if d_sums is not None else None,
                                                          _lib.launch_stream(stream, d_bank.device).cuda_stream))
         return d_pcm_out, d_sums
+
+    def set_seam(self, mode):
+        """SEAM_OFF (the default) or SEAM_STEADY: how the encodes that follow treat the loop seams (include/psxav_hip.h)"""
+        _lib.check(_bind().psxhip_spu_bank_set_seam(self._h, int(mode)))
+
+    def seam_passes(self, stream=None):
+        """The last encode's outcome per entry under SEAM_STEADY: an int32 CUDA tensor (n,), -1 = no seam block, k = fixed at pass k,
+        SEAM_PASSES = no fixed point (pass 0 kept).  Asynchronous."""
+        d_pass = _lib.new_tensor(stream, self.device, (self.n,), torch.int32)
+        _lib.check(_bind().psxhip_spu_bank_seam_passes_device(self._h, d_pass.data_ptr(), _lib.launch_stream(stream, self.device).cuda_stream))
+        return d_pass
+
+    def seam_report(self, d_bank, d_ref_pcm=None, stream=None):
+        """The loop seams of the bank in the uint8 CUDA tensor d_bank, judged from its bytes (and, with d_ref_pcm, against the entries'
+        PCM): a uint8 CUDA tensor (n, 40) of psxhip_spu_seam_t; ``seam_records`` turns it into a numpy record array.  Asynchronous."""
+        assert d_bank.dtype == torch.uint8 and d_bank.is_contiguous() and d_bank.numel() >= self.total
+        if d_ref_pcm is not None:
+            assert d_ref_pcm.dtype == torch.int16 and d_ref_pcm.is_contiguous() and d_ref_pcm.numel() >= self.pcm_elements
+        d_seam = _lib.new_tensor(stream, d_bank.device, (self.n, C.sizeof(SpuSeam)), torch.uint8)
+        _lib.check(_bind().psxhip_spu_bank_seam_device(self._h, d_bank.data_ptr(), d_ref_pcm.data_ptr() if d_ref_pcm is not None else None,
+                                                       d_seam.data_ptr(), _lib.launch_stream(stream, d_bank.device).cuda_stream))
+        return d_seam
+
+    @staticmethod
+    def seam_records(d_seam):
+        """seam_report's tensor as a numpy record array of SEAM_DTYPE (synchronises)"""
+        return d_seam.cpu().numpy().reshape(-1).view(SEAM_DTYPE)
 
     @staticmethod
     def snr_db(sums):
