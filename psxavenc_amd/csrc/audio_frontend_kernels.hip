@@ -48,8 +48,8 @@ struct Header {
     int mix[8][8];
     const void* src[8];
 };
-constexpr int kHeader = sizeof(Header) / 4;
-static_assert(sizeof(Header) == 320, "80 dwords before the table");
+constexpr int kHeader = kAfeHeaderDwords;
+static_assert(sizeof(Header) == kAfeHeaderBytes, "afe_layout.h: 80 dwords before the table");
 
 // mixed samples y_c at relative input index j (spec step 2); j < 0 reads the history, j >= n_in reads zero
 template <int DCH>
@@ -144,9 +144,9 @@ __global__ void __launch_bounds__(PSXHIP_AFE_TILE) afe_kernel(const psxhip_afe_j
     }
 
     const int T = a.T, H = a.H, L = a.L, M = a.M, P = a.P;
-    // LDS: [the header, 80 dwords] [the coefficient table, P * T / 2 dwords, when COEF_LDS] then per channel the span (span / 2
-    // dwords) and its shifted copy
-    uint32_t* ybuf = lds + kHeader + (COEF_LDS ? (P * T) >> 1 : 0);
+    // LDS (afe_layout.h): [the header, 80 dwords] [the coefficient table, P * T / 2 dwords, when COEF_LDS] then per channel the span
+    // (span / 2 dwords) and its shifted copy
+    uint32_t* ybuf = lds + kHeader + afe_table_dwords(COEF_LDS, P, T);
     int16_t* y16 = (int16_t*)ybuf;
     const uint32_t* coef32 = (const uint32_t*)a.coef;
     if (COEF_LDS) {
@@ -275,8 +275,7 @@ const void* kernel_for(int dch, int coef_lds) {
 }  // namespace
 
 extern "C" size_t psxhip_afe_lds_bytes(const psxhip_afe_job_t* j) {
-    if (j->bypass) return sizeof(Header);
-    return sizeof(Header) + (j->coef_lds ? (size_t)j->P * j->T * 2 : 0) + (size_t)j->dch * 2 * j->span * 2;
+    return afe_lds_bytes(j->bypass != 0, j->coef_lds != 0, j->P, j->T, j->dch, j->span);
 }
 
 extern "C" hipError_t psxhip_afe_prepare(int dch, int coef_lds, size_t lds_bytes) {

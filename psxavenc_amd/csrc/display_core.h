@@ -5,7 +5,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define DISP_FN __host__ __device__ __forceinline__
+#define DISP_FN __host__ __device__ inline __attribute__((always_inline))      /* (__forceinline__, spelt out: hip_runtime.h need not be included first) */
 #else
 #define DISP_FN static inline
 #endif

@@ -80,7 +80,10 @@ __global__ __launch_bounds__(256) void scaler_kernel(const psxhip_scaler_job_t j
     const int lxa = job.lh.left[X0], lxb = job.lh.left[X1 - 1] + job.lh.taps;
     const int cxa = job.ch.left[cX0], cxb = job.ch.left[cX0 + cw - 1] + job.ch.taps;
 
-    // ---- LDS: three byte planes (the rows a tile adds), the two rings of intermediates, the taps
+    // ---- LDS: three byte planes (the rows a tile adds), the two rings of intermediates, the taps.  scaler_layout.h's scaler_lds()
+    //      states this carve region by region, and the host sizes the launch by its total: a region added or resized here is added
+    //      there.  (The kernel keeps its own pointer chain: placed by scaler_lds()'s offsets it compiled to another instruction stream.)
+    static_assert(kScalerPlanePad == 8 && kScalerTileRowBytes == 4 * sizeof(int32_t), "scaler_layout.h: the planes' padding, t_rows' four dwords per tile");
     const int plane_bytes = (job.reg_rows * job.reg_cols + 8 + 15) & ~15;
     const int cplane_bytes = FMT == 0 ? plane_bytes : ((job.creg_rows * job.creg_cols + 8 + 15) & ~15);
     uint8_t* p0 = (uint8_t*)smem;

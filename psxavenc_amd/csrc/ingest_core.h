@@ -7,7 +7,7 @@
 #include <stdint.h>
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
-#define ING_FN __host__ __device__ __forceinline__
+#define ING_FN __host__ __device__ inline __attribute__((always_inline))      /* (__forceinline__, spelt out: hip_runtime.h need not be included first) */
 #else
 #define ING_FN static inline
 #endif

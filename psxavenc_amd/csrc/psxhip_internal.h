@@ -5,7 +5,9 @@
 #include <stdint.h>
 
 #include "../../include/psxav_hip.h"
+#include "afe_layout.h"
 #include "mdec_plan.h"
+#include "scaler_layout.h"
 
 /* bumped with every change to the MDEC kernel: bench.py keys the committed PMC summaries on it (profiles/pmc_index.json) */
 #define PSXHIP_MDEC_KERNEL_REV "mdec-k3.11"
@@ -94,54 +96,12 @@ int psxhip_adpcm_chunked_threshold(int n_chains);
 /* ... and with every change to the audio front-end kernel (audio_frontend_kernels.hip) */
 #define PSXHIP_AFE_KERNEL_REV "afe-k1.2"
 
-/* one launch of the audio front-end (audio_frontend_kernels.hip): n_out outputs of a stream, from the filter history and n_in
- * new source samples.  Indices are relative to the launch's first new sample; history sample h of channel c is y[h - (T - 1)]. */
-#define PSXHIP_AFE_TILE 256                 /* outputs per tile = threads per workgroup */
-typedef struct {
-	const void *src[8];                 /* interleaved: src[0] only */
-	int fmt, sch, dch;
-	int bypass;                         /* equal rates: y copied, no filter, no history */
-	int64_t n_in, n_out;                /* n_in <= 2^28 (the host cuts longer calls); n_out up to 16x that: indices are int64 */
-	int64_t i0;                         /* input index of output 0 (>= -H) */
-	int r0;                             /* (its absolute index * M) mod L */
-	int L, M, P, T, H;
-	const int16_t *coef;                /* [P][T] Q15 taps, device memory */
-	int coef_lds;                       /* 1: the table is copied into LDS once per workgroup */
-	int span;                           /* int16 per channel per copy in LDS: >= (L - 1 + (TILE - 1) M) / L + T, even */
-	const int16_t *hist_in;             /* [dch][T - 1] */
-	int16_t *hist_out;                  /* [dch][T - 1], written by the launch (the last tile) */
-	int16_t *dst;                       /* [n_out][dch] */
-	int16_t mix[8][8];                  /* [dst][src] Q14 */
-} psxhip_afe_job_t;
+/* the job and its LDS working set: afe_layout.h */
 size_t psxhip_afe_lds_bytes(const psxhip_afe_job_t *j);
 hipError_t psxhip_afe_prepare(int dch, int coef_lds, size_t lds_bytes);
 hipError_t psxhip_afe_launch(const psxhip_afe_job_t *j, int grid, void *stream);
 
-/* the scaler (frontend_kernels.hip; C ABI: psxhip_scaler.cpp) */
-typedef struct {              /* one separable filter bank on the device */
-	const int32_t *left;      /* [n] */
-	const int16_t *coef;      /* [n * taps] */
-	const uint32_t *digits;   /* [n * 2 * taps4] horizontal banks: the taps as two balanced int8 digits (c = 256 h + l), four taps
-	                           *                 to a dword, zero-padded to taps4 dwords: first the l dwords, then the h dwords */
-	int taps, taps4;
-} psxhip_scaler_bank_t;
-
-typedef struct {
-	const uint8_t *src;
-	size_t src_stride;
-	uint8_t *out;
-	size_t frame_stride;
-	int sw, sh, dw, dh;
-	int limited;              /* YUV input in MPEG range: expand on the intermediates */
-	psxhip_scaler_bank_t lh, lv, ch, cv;      /* luma / chroma, horizontal / vertical */
-	int csw, csh;             /* chroma source plane size (sw/2 x sh/2 for YUV420P, sw x sh for RGB) */
-	int TW, TH;               /* luma tile; the chroma tile is TW/2 x TH/2 */
-	int tiles_x, tiles_y;
-	int vsegs;                /* vertical segments per band (blockIdx.z): each re-reads the rows its first tile reaches */
-	int reg_rows, reg_cols;   /* LDS region capacity per plane (RGB: the union of the luma and chroma reach; YUV: luma) */
-	int creg_rows, creg_cols; /* ... of a chroma plane (YUV) */
-} psxhip_scaler_job_t;
-
+/* the scaler (frontend_kernels.hip; C ABI: psxhip_scaler.cpp); the job and its LDS working set: scaler_layout.h */
 /* lets the kernel of this source format (yuv: YUV420P, else RGB24) take up to max_lds bytes of dynamic LDS */
 hipError_t psxhip_scaler_prepare(int yuv, int max_lds);
 /* n_frames (<= 65535) frames from j->src on: grid = tiles_x bands x n_frames x vsegs */
